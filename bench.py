@@ -237,7 +237,13 @@ def parse(argv=None):
     ap.add_argument("--no-shard-check", action="store_true", help="skip the sharded == unsharded recomputation after the timed region")
     ap.add_argument("--no-extras", action="store_true", help="skip the latency and other-config sub-records")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: launcher, rendezvous (gloo), shard plan, collective, JSON relay")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the logits the last timed step computed (rank 0's items) to DIR/<name>.npy as float32: "
+                         "item 0 of half-batch A whole and a fixed seeded sample of every half-batch's cls / loc (dump_outputs; under 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1 (the number of timed steps)")
+    return args
 
 
 def cpu_baseline(model_state, gnn_iters, budget_s=20.0):
@@ -751,6 +757,33 @@ def shard_check_plan(rows, Bh, n_frames=8):
     return frames, pairs
 
 
+DUMP_SAMPLE = 1 << 21          # elements per sampled array (8 MB as float32)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outs, out_dir):
+    """--dump-outputs: what the timed path returned in its last step, for comparing two builds output for output.  `outs` = the per-half-batch
+    {'cls', 'loc'} of this rank's items (Workload.outputs).  Written as float32 .npy: `<key>_item0` = item 0 of half-batch A whole, and
+    `<key>_<half>_sample` = the elements at DUMP_SAMPLE sorted flat indices drawn from a generator seeded by (half, key) -- the same
+    indices in every run with the same arguments (the whole output is ~8 GB at the default workload).  -> {name: shape}"""
+    arrays = {}
+    for hi, (half, out) in enumerate(zip("ab", outs)):
+        for ki, key in enumerate(("cls", "loc")):
+            x = out[key]
+            if hi == 0:
+                arrays["%s_item0" % key] = x[0]
+            flat = x.reshape(-1)
+            idx = np.sort(np.random.default_rng([hi, ki]).integers(0, flat.numel(), DUMP_SAMPLE))
+            arrays["%s_%s_sample" % (key, half)] = flat[torch.from_numpy(idx).to(flat.device)]
+    total = sum(4 * v.numel() for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.detach().float().cpu().numpy())
+    print("bench.py: %d output arrays (%.1f MB) written to %s" % (len(arrays), total / 2**20, out_dir), file=sys.stderr, flush=True)
+    return {name: tuple(v.shape) for name, v in arrays.items()}
+
+
 class Workload:
     """One benchmark workload: `frames_total` synthetic 5-agent frames per step over the whole job, run as two half-batches, agent-sharded over the
     active ranks (v2x_sim_amd/parallel.py).  measure() = warm-up, hipGraph capture, the timed K steps between barriers, then the correctness
@@ -1093,6 +1126,8 @@ def main():
     else:
         wl = Workload(ctx, args.frames_per_gpu * sworld)
     res = wl.measure()
+    if args.dump_outputs and rank == 0 and active:
+        dump_outputs(wl.outputs(), args.dump_outputs)
     Bt, fps, ms_per_step, exec_mode, mode = wl.Bt, res["fps"], res["ms_per_step"], wl.exec_mode, wl.mode
     graph_equals_eager, sharded_equals_unsharded = res["graph_equals_eager"], res["sharded_equals_unsharded"]
     exposed_all, ranks_seen = res["exposed_all"], res["ranks_seen"]

@@ -274,3 +274,32 @@ echo "\\"void %s(StreamArgs)\\",\\"$c\\",$v" >> "$f"
     assert "AFTER the timed run" in roof["traffic_source"] and roof["pmc_passes_s"] >= 0.0
     assert list(rec)[-1] == "summary" and lines[0].rstrip().endswith('"summary": {"headline_frames_per_s": 6500.0}}')
     assert rec["value"] == 6500.0 and rec["cpu_baseline"] == {"value": 2.0}
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_logits(tmp_path):
+    """--dump-outputs (bench.py: dump_outputs): float32 .npy files, under 64 MB at the bench geometry, item 0 of half-batch A whole, and a sample
+    of every half-batch's cls / loc at indices that are the same in every run; --steps below 1 is refused."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.parse(["--dump-outputs", str(tmp_path), "--steps", "3"]).dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    # the bench geometry's shapes (320 items per half-batch, 256 x 256 x 6 anchors) with the items dimension cut to 3
+    g = torch.Generator().manual_seed(0)
+    outs = [{"cls": torch.randn((3, 256 * 256 * 6, 2), generator=g), "loc": torch.randn((3, 256, 256, 6, 1, 6), generator=g)} for _ in range(2)]
+    shapes = bench.dump_outputs(outs, str(tmp_path / "a"))
+    assert sorted(shapes) == ["cls_a_sample", "cls_b_sample", "cls_item0", "loc_a_sample", "loc_b_sample", "loc_item0"]
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n in shapes)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["loc_item0"], outs[0]["loc"][0].numpy()) and got["cls_b_sample"].shape == (bench.DUMP_SAMPLE,)
+    idx = np.sort(np.random.default_rng([1, 0]).integers(0, outs[1]["cls"].numel(), bench.DUMP_SAMPLE))
+    assert np.array_equal(got["cls_b_sample"], outs[1]["cls"].reshape(-1).numpy()[idx])
+    bench.dump_outputs(outs, str(tmp_path / "b"))
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy"))) for k, v in got.items())
