@@ -19,9 +19,10 @@ Execution mode is the SAME for every N (`exec_mode` in the record): the step's f
 (own graph memory pools) and are joined at the end of the step: one half's kernels fill the tails and the HBM-bound
 phases of the other (+2.3...3.0 % at N = 1 against `--graph 4`, the one-stream order).
 
-Prints ONE JSON line (rank 0).  `roofline` is computed from HIP events recorded live around every
-kernel launch of an instrumented pass on the launch stream; `cpu_baseline` times the CPU oracle
-(oracle/, PyTorch-CPU fp32) on a bounded sample of the same workload.
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs and nothing else: set-up, warm-up, the K timed steps,
+`--dump-outputs`, the line.  `--full` adds everything else the benchmark measures or checks, after the timed region and in runs of
+their own: `roofline` is computed from HIP events recorded live around every kernel launch of an instrumented pass on the launch
+stream; `cpu_baseline` times the CPU oracle (oracle/, PyTorch-CPU fp32) on a bounded sample of the same workload; parse() lists the rest.
 """
 import argparse
 import json
@@ -115,8 +116,7 @@ def live_traffic_table(args):
     for counter, factor in (("FETCH_SIZE", 1024.0), ("WRITE_SIZE", 1024.0)):       # KiB -> bytes; the FETCH_SIZE calibration factor is applied per kernel in apply_live_traffic
         out = tempfile.mkdtemp(prefix="v2x_pmc_", dir="/tmp")
         cmd = [rocprof, "--pmc", counter, "-d", out, "-o", "p", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
-               "--steps", "2", "--warmup", "1", "--graph", "0", "--frames-per-gpu", str(args.frames_per_gpu), "--gnn-iters", str(args.gnn_iters),
-               "--no-cpu-baseline", "--no-gpu-baseline", "--no-extras", "--no-calibration", "--no-shard-check", "--no-roofline"]
+               "--steps", "2", "--warmup", "1", "--graph", "0", "--frames-per-gpu", str(args.frames_per_gpu), "--gnn-iters", str(args.gnn_iters)]
         env = dict(os.environ, TMPDIR="/tmp", V2X_BENCH_LIVE_TRAFFIC="0", V2X_BENCH_INNER="1")
         try:
             proc = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
@@ -214,6 +214,11 @@ def parse(argv=None):
                     help="frames per step and GPU (two half-batches of 64 = 320 maps: every conv layer then splits into a "
                          "whole number of rounds of 256 workgroups; 64 frames/GPU leaves the 32x32 layers at 2.5 rounds, -4 %%)")
     ap.add_argument("--gnn-iters", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures or checks (minutes): graph == eager and sharded == unsharded, "
+                         "the instrumented roofline pass with its two counter passes, the calibration probes, latency / other configs / training / host streaming, "
+                         "the stock PyTorch-ROCm and CPU baselines, the strong-scaling workload at N > 1.  Without it none of them runs and their keys in the "
+                         "line are null; the --no-* options below drop single legs of a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gpu-baseline", action="store_true", help="skip the same-node stock PyTorch-ROCm comparator (`gpu_stock_baseline`)")
     ap.add_argument("--no-roofline", action="store_true")
@@ -232,7 +237,7 @@ def parse(argv=None):
                          "agent-per-gpu: the north_star's literal layout -- rank a < 5 owns agent a's frames, ranks >= 5 idle "
                          "(needs N >= 5; frames = frames_per_gpu * 5)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
-                    help="weak (default, the headline): per-GPU work fixed, frames per step = frames_per_gpu * N; when N > 1 the strong workload is timed as "
+                    help="weak (default, the headline): per-GPU work fixed, frames per step = frames_per_gpu * N; when N > 1 a --full run times the strong workload as "
                          "well and printed as the sub-record `strong`.  strong: total work fixed at frames_per_gpu frames per step whatever N")
     ap.add_argument("--no-shard-check", action="store_true", help="skip the sharded == unsharded recomputation after the timed region")
     ap.add_argument("--no-extras", action="store_true", help="skip the latency and other-config sub-records")
@@ -243,6 +248,9 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be >= 1 (the number of timed steps)")
+    if not args.full:
+        args.no_cpu_baseline = args.no_gpu_baseline = args.no_roofline = args.no_live_traffic = True
+        args.no_calibration = args.no_shard_check = args.no_extras = True
     return args
 
 
@@ -786,7 +794,7 @@ def dump_outputs(outs, out_dir):
 
 class Workload:
     """One benchmark workload: `frames_total` synthetic 5-agent frames per step over the whole job, run as two half-batches, agent-sharded over the
-    active ranks (v2x_sim_amd/parallel.py).  measure() = warm-up, hipGraph capture, the timed K steps between barriers, then the correctness
+    active ranks (v2x_sim_amd/parallel.py).  measure() = warm-up, hipGraph capture, the timed K steps between barriers, then (--full) the correctness
     checks of what was timed: graph == eager (N = 1) and sharded == unsharded (every N; below)."""
 
     def __init__(self, ctx, frames_total, capture=True):
@@ -1000,8 +1008,8 @@ class Workload:
         torch.cuda.synchronize()
         self.barrier()
         elapsed = time.perf_counter() - t0
-        graph_equals_eager = None           # checked at N = 1 in the graph modes
-        if self.mode in (1, 4, 5) and self.active and not self.use_dist:
+        graph_equals_eager = None           # checked at N = 1 in the graph modes of a --full run
+        if args.full and self.mode in (1, 4, 5) and self.active and not self.use_dist:
             # the graphs' outputs (the last replay; the two halves ran concurrently in mode 1) against an eager, one-stream recomputation of the same
             # step: every kernel is deterministic and the halves are independent, so the logits must agree bit for bit
             ref = self.step()
@@ -1118,7 +1126,7 @@ def main():
                active=active, model=model)
     _mark(MARK_READY)       # (supervised N > 1 runs: model, data generator and process group are up; what follows has collectives in it)
     # weak scaling (the headline, per-GPU work fixed): frames = frames_per_gpu * ranks; strong scaling (total work fixed): frames = frames_per_gpu
-    # whatever N.  `--scaling weak` (default) times the weak workload and, when N > 1, the strong one as well (sub-record `strong`).
+    # whatever N.  `--scaling weak` (default) times the weak workload and, when N > 1 in a --full run, the strong one as well (sub-record `strong`).
     if args.scaling == "strong":
         if (args.frames_per_gpu // 2 * AGENTS) % sworld:
             raise SystemExit("--scaling strong: %d items per half-batch do not divide over %d ranks" % (args.frames_per_gpu // 2 * AGENTS, sworld))
@@ -1133,7 +1141,7 @@ def main():
     exposed_all, ranks_seen = res["exposed_all"], res["ranks_seen"]
     step, halves = wl.step, wl.halves
     strong = None
-    if args.scaling == "weak" and world > 1 and (args.frames_per_gpu // 2 * AGENTS) % sworld == 0:
+    if args.full and args.scaling == "weak" and world > 1 and (args.frames_per_gpu // 2 * AGENTS) % sworld == 0:
         wl.release()
         ws = Workload(ctx, args.frames_per_gpu)
         rs = ws.measure()
@@ -1300,7 +1308,7 @@ def main():
         rec = {
             "metric": "BEV frames/sec, V2VNet 5-agent detection (256x256 BEV)", "value": fps, "unit": "frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "bf16",
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "bf16", "full": args.full,
             "data": "synthetic (seeded 65536-pt sweeps per agent, random SE(2) poses, He-init weights)",
             "config": {"workload": "V2VNet 5-agent detection, points->logits (a1-a7), gnn_iter=%d" % args.gnn_iters,
                        "agents": AGENTS, "frames_per_step": Bt, "frames_per_gpu": Bt // max(sworld, 1),

@@ -154,9 +154,10 @@ def test_live_traffic_measurement_is_optional_and_fails_soft(monkeypatch, tmp_pa
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
-    args = bench.parse(["--no-live-traffic"])
-    assert bench.live_traffic_table(args) == (None, "switched off", 0.0) and bench.live_traffic_wanted(args) == (False, "switched off")
-    args = bench.parse([])
+    for flags in (["--full", "--no-live-traffic"], []):        # (a plain run takes no counter passes)
+        args = bench.parse(flags)
+        assert bench.live_traffic_table(args) == (None, "switched off", 0.0) and bench.live_traffic_wanted(args) == (False, "switched off")
+    args = bench.parse(["--full"])
     monkeypatch.setenv("V2X_BENCH_LIVE_TRAFFIC", "0")
     assert bench.live_traffic_table(args)[0] is None
     monkeypatch.delenv("V2X_BENCH_LIVE_TRAFFIC")
@@ -212,7 +213,7 @@ def test_n1_orchestrator_runs_the_bench_child_first_and_merges_the_counter_passe
     fake.write_text("#!/bin/sh\necho pmc-pass-ran >> %s\nexit 7\n" % (tmp_path / "calls"))
     fake.chmod(0o755)
     env = {"V2X_BENCH_LIVE_TRAFFIC": "1", "V2X_BENCH_FORCE_ORCHESTRATE": "1", "PATH": str(tmp_path) + os.pathsep + os.environ["PATH"]}
-    p = _run("--steps", "1", "--warmup", "0", env_extra=env)
+    p = _run("--steps", "1", "--warmup", "0", "--full", env_extra=env)
     assert p.returncode == 3 and "needs the MI355X" in p.stderr and '{"metric"' not in p.stdout
     assert not (tmp_path / "calls").exists()        # no record from the child -> no counter pass is started
 
@@ -262,7 +263,7 @@ echo "\\"void %s(StreamArgs)\\",\\"$c\\",$v" >> "$f"
 """ % kern)
     fake.chmod(0o755)
     env = {"V2X_BENCH_FORCE_ORCHESTRATE": "1", "V2X_BENCH_FAKE_RECORD": str(rec_path), "V2X_BENCH_LIVE_TRAFFIC": "1", "PATH": str(tmp_path) + os.pathsep + os.environ["PATH"]}
-    p = _run("--steps", "20", "--warmup", "5", env_extra=env)
+    p = _run("--steps", "20", "--warmup", "5", "--full", env_extra=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1
@@ -274,6 +275,32 @@ echo "\\"void %s(StreamArgs)\\",\\"$c\\",$v" >> "$f"
     assert "AFTER the timed run" in roof["traffic_source"] and roof["pmc_passes_s"] >= 0.0
     assert list(rec)[-1] == "summary" and lines[0].rstrip().endswith('"summary": {"headline_frames_per_s": 6500.0}}')
     assert rec["value"] == 6500.0 and rec["cpu_baseline"] == {"value": 2.0}
+
+
+def test_a_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full every side measurement and check is off, whatever --no-* options say, and the run is ONE process: no orchestrator, no child,
+    no counter pass (here, where the orchestrator is forced on and a stand-in child record is on offer, it goes straight to the GPU and finds none).
+    With --full the legs are on and each --no-* option drops its own."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod4", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    legs = ("no_cpu_baseline", "no_gpu_baseline", "no_roofline", "no_live_traffic", "no_calibration", "no_shard_check", "no_extras")
+    plain, full, part = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"]), bench.parse(["--full"]), bench.parse(["--full", "--no-extras"])
+    assert not plain.full and all(getattr(plain, k) for k in legs)
+    assert full.full and not any(getattr(full, k) for k in legs)
+    assert [k for k in legs if getattr(part, k)] == ["no_extras"]
+    assert (plain.steps, plain.warmup, plain.graph, plain.frames_per_gpu) == (full.steps, full.warmup, full.graph, full.frames_per_gpu)
+    rec_path = tmp_path / "child.json"
+    rec_path.write_text('{"metric": "canned"}')
+    fake = tmp_path / "rocprofv3"
+    fake.write_text("#!/bin/sh\necho pmc-pass-ran >> %s\nexit 7\n" % (tmp_path / "calls"))
+    fake.chmod(0o755)
+    env = {"V2X_BENCH_LIVE_TRAFFIC": "1", "V2X_BENCH_FORCE_ORCHESTRATE": "1", "V2X_BENCH_FAKE_RECORD": str(rec_path),
+           "PATH": str(tmp_path) + os.pathsep + os.environ["PATH"]}
+    p = _run("--gpus", "1", "--steps", "1", "--warmup", "0", env_extra=env)
+    assert p.returncode == 3 and "needs the MI355X" in p.stderr and '{"metric"' not in p.stdout
+    assert not (tmp_path / "calls").exists()
 
 
 def test_dump_outputs_writes_a_fixed_sample_of_the_logits(tmp_path):

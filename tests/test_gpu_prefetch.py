@@ -36,7 +36,7 @@ def test_prefetcher_order_values_and_errors(device):
 def test_streaming_from_host_gives_the_resident_logits(device):
     """The three input arms of tools/stream_points.py (sweeps resident in HBM, copied inside the step, prefetched on a copy stream by
     DevicePrefetcher) must produce the same logits bit for bit: a copy overlapped with the previous step's kernels may not be read early.
-    (The RATES of the three arms are a measurement, not a parity property: bench.py prints them as `host_streaming`.)"""
+    (The RATES of the three arms are a measurement, not a parity property: bench.py --full prints them as `host_streaming`.)"""
     tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
     spec = importlib.util.spec_from_file_location("stream_points", os.path.join(tools, "stream_points.py"))
     mod = importlib.util.module_from_spec(spec)
@@ -45,7 +45,7 @@ def test_streaming_from_host_gives_the_resident_logits(device):
     assert set(res) == {"resident", "inline", "prefetch"} and all(v > 0 for v in res.values())
     # a loose STRUCTURAL bound, not a performance claim: a regression that serialises the copy stream behind the compute stream -- or
     # blocks the producer thread -- would show as the prefetched arm falling far below the resident one (each arm is the best of two passes;
-    # measured 0.85-0.95 at this size).  The gated number stays bench.py's `host_streaming`.
+    # measured 0.85-0.95 at this size).  The gated number stays bench.py --full's `host_streaming`.
     assert res["prefetch"] >= 0.4 * res["resident"], res
     for arm in ("inline", "prefetch"):
         for k in ("cls", "loc"):

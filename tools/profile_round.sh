@@ -32,7 +32,7 @@ fi
 TAG=${1:-vX}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python3 bench.py --steps 20 --warmup 3 --graph 0 --no-cpu-baseline --no-gpu-baseline --no-extras --no-calibration --no-shard-check > $OUT/kt.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -d $OUT/pf -o pf --output-format csv -- python3 bench.py --steps 2 --warmup 1 --graph 0 --no-cpu-baseline --no-gpu-baseline --no-extras --no-calibration --no-shard-check --no-roofline > $OUT/pf.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -d $OUT/pw -o pw --output-format csv -- python3 bench.py --steps 2 --warmup 1 --graph 0 --no-cpu-baseline --no-gpu-baseline --no-extras --no-calibration --no-shard-check --no-roofline > $OUT/pw.log 2>&1

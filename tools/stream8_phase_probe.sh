@@ -8,7 +8,7 @@ OUT=gpurun_out/stream8_probe.txt
 mkdir -p gpurun_out; : > $OUT
 for d in 0 1 2 3 4 8 7; do
     probe_build conv_stream "-DV2X_STREAM_DBG_BUILD=$d"
-    python bench.py --no-cpu-baseline --no-gpu-baseline --no-live-traffic --no-extras --steps 10 --warmup 2 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-gpu-baseline --no-live-traffic --no-extras --steps 10 --warmup 2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']
 print('dbg=$d', {n.replace('conv3x3_','').replace('_kernel',''): round(v['us_per_step']/v['launches_per_step'],1) for n,v in k.items() if 'stream8' in n})" >> $OUT
