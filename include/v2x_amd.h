@@ -344,7 +344,7 @@ int v2x_bn_train_backward_dxsum(const uint16_t *x, const uint16_t *dy, long long
  * mode:  V2X_FUSE_WSUM  out = sum_j coef*warp_j ;  V2X_FUSE_MEAN  out = (sum_{coef!=0} warp_j) / count ;
  *        V2X_FUSE_MAX   out = max_{coef!=0} warp_j  (elementwise; the zero padding of a warped map takes part, as in
  *        upstream's torch.max(torch.stack(...)) of MaxFusion)
- * out:   bf16 NHWC [n_out][H][W][C].   C % 8 == 0. */
+ * out:   bf16 NHWC [n_out][H][W][C].   C % 8 == 0.   n_out == 0: returns V2X_OK, nothing is launched; items / coef / out may be NULL then. */
 enum { V2X_FUSE_WSUM = 0, V2X_FUSE_MEAN = 1, V2X_FUSE_MAX = 2 };
 int v2x_warp_fuse(const uint16_t *feat, int A, int Bt, int H, int W, int C, const float *trans,
                   const int32_t *items, int n_out, const float *coef, int mode, uint16_t *out,

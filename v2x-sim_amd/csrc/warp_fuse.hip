@@ -580,12 +580,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 static int warp_fuse_impl(const uint16_t *feat, int A, int Bt, int H, int W, int C, const float *trans,
                           const int32_t *items, int n_out, const float *coef, int mode, uint16_t *out,
                           const int32_t *order, int order_stride, int order_len, v2x_stream_t stream) {
-    V2X_REQUIRE(feat && trans && items && coef && out, "v2x_warp_fuse: null pointer");
+    V2X_REQUIRE(feat && trans, "v2x_warp_fuse: null pointer");
     V2X_REQUIRE(A > 0 && A <= 32 && Bt > 0 && H > 0 && W > 0, "v2x_warp_fuse: bad dims");
     V2X_REQUIRE(C > 0 && C % 8 == 0, "v2x_warp_fuse: C=%d must be a multiple of 8", C);
     V2X_REQUIRE(mode == V2X_FUSE_WSUM || mode == V2X_FUSE_MEAN || mode == V2X_FUSE_MAX, "v2x_warp_fuse: bad mode");
     V2X_REQUIRE(n_out >= 0 && n_out <= 65535, "v2x_warp_fuse: n_out out of range");
-    if (n_out == 0) return V2X_OK;
+    if (n_out == 0) return V2X_OK;   // nothing to write; the (empty) items / coef / out buffers of a caller are null pointers then
+    V2X_REQUIRE(items && coef && out, "v2x_warp_fuse: null pointer");
     if (v2x_tune(V2X_TUNE_WARP_LDS) >= 2 && H % WL_T == 0 && W % WL_T == 0 && C % WL_CW == 0 && (long long)H * W < (1ll << 30)) {
         // the shared-set-up form (default); WARP_LDS = 1 keeps the per-item set-ups (A/B runs, bitwise test), 0 the direct form
         dim3 grid((H / WL_T) * (W / WL_T), n_out, C / WL_CW);
