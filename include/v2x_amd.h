@@ -284,6 +284,31 @@ int v2x_conv2d(const v2x_conv_desc *desc, v2x_stream_t stream);
  * output is never stored (first->out ignored); the logits are bit-identical to v2x_conv2d(first) followed by v2x_conv2d(second). */
 int v2x_conv2d_pair(const v2x_conv_desc *first, const v2x_conv_desc *second, v2x_stream_t stream);
 
+/* ---------------------------------------------------------------- communication codec (compress_level = k; codec.hip)
+ * Upstream Backbone.py::LidarEncoder with compress_level = k > 0 wraps the transmitted map x_3 in com_compresser / bn_compress / ReLU and
+ * com_decompresser / bn_decompress / ReLU (two 1x1 Conv2d, C -> Cc = C >> k -> C); DESIGN.md section 3 freezes the specification.
+ *     msg[p][:] = relu(scale_c * (Wc x[p][:]) + shift_c)  rounded to bf16  -- the MESSAGE an agent sends: [M][Cc] bf16, natural channel order
+ *     y[p][:]   = relu(scale_d * (Wd msg[p][:]) + shift_d) rounded to bf16
+ * x, y: [M][C] bf16 NHWC pixels, C = 128 or 256, Cc a power of two in [1, C / 2], 0 < M < 2^31 - 64 (any M: no multiple of 16 needed); every pointer
+ * 16-byte aligned.  v2x_codec_1x1 does both in one launch, the message stays in registers and goes to `msg` only when msg != NULL;
+ * v2x_codec_compress is the sender's half, v2x_codec_decompress the receiver's.  decompress(compress(x)) is BIT-IDENTICAL to the fused launch, and
+ * the bits of a pixel depend on that pixel alone (not on M or on its position in the launch).  fp32 accumulation over ascending 32-channel chunks.
+ * Weights: one packed buffer of MFMA A fragments, [fragment][lane = 16 q + j][8] bf16, CT1 = max(Cc / 16, 1), KS2 = max(Cc / 32, 1):
+ *     stage one, fragments (i, ks), i < CT1, ks < C / 32:   element e = Wc[16 i + j][32 ks + 8 q + e]            (rows >= Cc are zero)
+ *     stage two, fragments (i, c),  i < C / 16, c < KS2:    element e = 4 h + r = Wd[16 i + j][32 c + 16 h + 4 q + r]   (columns >= Cc are zero)
+ * -- stage two's K slots are in the chain order of stage one's accumulators ("weight layouts" above), so the message feeds it from registers.
+ * Then fp32 `ss`: scale_c[16 CT1], shift_c[16 CT1] (padding rows 1 / 0), scale_d[C], shift_d[C].  v2x_pack_codec_size -> bf16 elements of the
+ * weight buffer (and the floats of `ss`), or V2X_EINVAL (the same C and Cc as the launches); v2x_pack_codec runs on the HOST: wc [Cc][C], wd [C][Cc] fp32 row-major. */
+long long v2x_pack_codec_size(int C, int Cc, long long *ss_floats);
+int v2x_pack_codec(int C, int Cc, const float *wc, const float *scale_c, const float *shift_c, const float *wd, const float *scale_d,
+                   const float *shift_d, uint16_t *dst_w, float *dst_ss);
+int v2x_codec_1x1(const uint16_t *x, long long M, int C, int Cc, const uint16_t *wpack, const float *sspack, uint16_t *y, uint16_t *msg,
+                  v2x_stream_t stream);
+int v2x_codec_compress(const uint16_t *x, long long M, int C, int Cc, const uint16_t *wpack, const float *sspack, uint16_t *msg,
+                       v2x_stream_t stream);
+int v2x_codec_decompress(const uint16_t *msg, long long M, int C, int Cc, const uint16_t *wpack, const float *sspack, uint16_t *y,
+                         v2x_stream_t stream);
+
 /* ---------------------------------------------------------------- f-3: backward of the 3x3 stride-1 convolutions
  * Upstream trains through torch.autograd (cuDNN / MIOpen kernels behind nn.Conv2d.backward, tools/det/train_codet.py).
  *   data gradient:   dX = conv3x3(dY, W') with W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx] -- a forward convolution: v2x_conv2d

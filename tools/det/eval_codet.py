@@ -1,0 +1,24 @@
+#!/usr/bin/env python3
+"""tools/det/test_codet.py with the communication flags of upstream's driver:
+
+    python tools/det/eval_codet.py --data /path/V2X-Sim-det/test --com mean --resume ckpt.pth --compress_level 2 --only_v2i 1
+
+--compress_level k (0..8) and --only_v2i 0|1 reach the model's constructor and are checked against the record tools/det/train_codet.py
+keeps in its checkpoints; every other flag is test_codet.py's own (v2x_sim_amd/utils/comm.py::run_eval_driver)."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+for _p in (ROOT, os.path.join(ROOT, "v2x-sim_amd"), os.path.dirname(os.path.abspath(__file__))):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+
+def main(argv=None):
+    import test_codet
+    from v2x_sim_amd.utils import comm
+    return comm.run_eval_driver(test_codet.main, sys.argv[1:] if argv is None else argv)
+
+
+if __name__ == "__main__":
+    main()

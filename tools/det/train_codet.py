@@ -39,6 +39,8 @@ def build_parser():
     ap.add_argument("--log", action="store_true")
     ap.add_argument("--nworker", default=0, type=int, help="DataLoader workers (parsed dataset)")
     ap.add_argument("--rsu", default=1, type=int, help="parsed dataset: 1 = agent0 (the RSU) takes part, 0 = vehicles only")
+    from v2x_sim_amd.utils import comm
+    comm.add_arguments(ap)
     ap.add_argument("--engine", default="", choices=["", "torch", "hip", "hip-graph"],
                     help="training graph: torch = PyTorch-ROCm ops (fp32, MIOpen); hip = bf16 NHWC graph on the hand-written kernels "
                          "(V2X_TRAIN_HIP=1); hip-graph = the same with every step replayed as one hipGraph (V2X_TRAIN_GRAPH=1; FaFNet, and "
@@ -55,22 +57,25 @@ def main(argv=None):
     from v2x_sim_amd.configs import Config
     from v2x_sim_amd.models.det import CatFusion, DiscoNet, FaFNet, MaxFusion, MeanFusion, SumFusion, V2VNet, When2com
     from v2x_sim_amd.train.loop import init_for_training, make_optimizer, train_dataset, train_synthetic
+    from v2x_sim_amd.utils import comm
     if not torch.cuda.is_available():
         raise SystemExit("train_codet.py needs the MI355X")
     config = Config("train", binary=True, only_det=True)
     A = args.num_agent
+    ckw = comm.model_kwargs(args, intermediate=args.com not in ("lowerbound", "upperbound"))
     if args.com == "v2v":
-        model = V2VNet(config, gnn_iter_times=args.gnn_iter_times, layer=args.layer, num_agent=A)
+        model = V2VNet(config, gnn_iter_times=args.gnn_iter_times, layer=args.layer, num_agent=A, **ckw)
     elif args.com == "when2com":
-        model = When2com(config, layer=args.layer, num_agent=A)
+        model = When2com(config, layer=args.layer, num_agent=A, **ckw)
     elif args.com in ("sum", "mean", "max", "cat", "disco"):
         cls = {"sum": SumFusion, "mean": MeanFusion, "max": MaxFusion, "cat": CatFusion, "disco": DiscoNet}[args.com]
-        model = cls(config, layer=args.layer, kd_flag=0, num_agent=A)      # DiscoNet without the distillation teacher
+        model = cls(config, layer=args.layer, kd_flag=0, num_agent=A, **ckw)      # DiscoNet without the distillation teacher
     else:
         model = FaFNet(config, layer=args.layer, kd_flag=0, num_agent=A)
     ckpt = None
     if args.resume:
         ckpt = torch.load(args.resume, map_location="cpu")
+        comm.check_checkpoint(ckpt, args)
         model.load_state_dict(ckpt.get("model_state_dict", ckpt), strict=True)  # a key mismatch must not train from init silently
     else:
         init_for_training(model, seed=args.seed)
@@ -109,7 +114,7 @@ def main(argv=None):
         if args.logpath:
             os.makedirs(args.logpath, exist_ok=True)
             torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": opt.state_dict(),
-                        "scheduler_state_dict": sched.state_dict()}, os.path.join(args.logpath, "epoch_%d.pth" % epoch))
+                        "scheduler_state_dict": sched.state_dict(), **comm.checkpoint_fields(args)}, os.path.join(args.logpath, "epoch_%d.pth" % epoch))
     return model
 
 

@@ -44,6 +44,8 @@ def build_parser():
     ap.add_argument("--log", action="store_true")
     ap.add_argument("--rsu", default=1, type=int, help="parsed dataset: 1 = agent0 (the RSU) takes part, 0 = vehicles only")
     ap.add_argument("--resume", default="", type=str)
+    from v2x_sim_amd.utils import comm
+    comm.add_arguments(ap)
     return ap
 
 
@@ -53,16 +55,19 @@ def main(argv=None):
     from v2x_sim_amd.configs import Config
     from v2x_sim_amd.models.seg import FaFNetSeg, V2VNetSeg
     from v2x_sim_amd.train.loop import init_for_training
+    from v2x_sim_amd.utils import comm
     from v2x_sim_amd.utils.SegModule import SegModule
     if not torch.cuda.is_available():
         raise SystemExit("train_seg.py needs the MI355X")
     device = torch.device("cuda:0")
     config = Config("train", binary=True, only_det=True)
     A = args.num_agent
-    model = V2VNetSeg(config, num_agent=A) if args.com == "v2v" else FaFNetSeg(config, num_agent=A)
+    ckw = comm.model_kwargs(args, intermediate=args.com == "v2v")
+    model = V2VNetSeg(config, num_agent=A, **ckw) if args.com == "v2v" else FaFNetSeg(config, num_agent=A)
     ckpt = None
     if args.resume:
         ckpt = torch.load(args.resume, map_location="cpu")
+        comm.check_checkpoint(ckpt, args)
         model.load_state_dict(ckpt.get("model_state_dict", ckpt), strict=True)
     else:
         init_for_training(model, seed=args.seed)
@@ -100,8 +105,8 @@ def main(argv=None):
         print("epoch %d: mean loss of the last 20 steps %.4f" % (epoch, float(np.mean(losses[-20:]))))
         if args.logpath:
             os.makedirs(args.logpath, exist_ok=True)
-            torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": opt.state_dict()},
-                       os.path.join(args.logpath, "epoch_%d.pth" % epoch))
+            torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": opt.state_dict(),
+                        **comm.checkpoint_fields(args)}, os.path.join(args.logpath, "epoch_%d.pth" % epoch))
     model.eval()
     return model
 

@@ -115,6 +115,11 @@ SIGNATURES = {
     "v2x_conv_stream_tile_rows": (C.c_int, [C.c_int, C.c_int]),
     "v2x_conv2d": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     "v2x_conv2d_pair": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.c_void_p]),
+    "v2x_pack_codec_size": (C.c_longlong, [C.c_int, C.c_int, C.c_void_p]),
+    "v2x_pack_codec": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "v2x_codec_1x1": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v2x_codec_compress": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v2x_codec_decompress": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "v2x_conv3x3_wgrad_splits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "v2x_conv3x3_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                     C.c_void_p]),

@@ -76,10 +76,15 @@ class V2VNet(IntermediateModelBase):
             # upstream: torch.stack of an empty neighbour list raises for a 1-agent frame
             raise RuntimeError("V2VNet needs >= 2 agents in every frame (stack expects a non-empty TensorList)")
         coef = torch.zeros((len(items), A), dtype=torch.float32)
+        L = self.links(batch_size)
         for m, (a, f) in enumerate(items):
             for j in range(counts[f]):
-                if j != a:
+                if j != a and (L is None or L[f][a][j]):
                     coef[m, j] = 1.0
+            if not bool(coef[m].any()):
+                # an ego without an incoming link has the empty neighbour list of a one-agent frame
+                raise RuntimeError("V2VNet needs >= 1 linked neighbour for every ego (stack expects a non-empty TensorList): "
+                                   "agent %d of frame %d has none under the link mask" % (a, f))
         full = len(items) == A * batch_size
         return {"items": ops.items_tensor(items, A, batch_size, device),
                 "coef": coef.to(device), "rows": None if full else torch.tensor(rows, device=device),

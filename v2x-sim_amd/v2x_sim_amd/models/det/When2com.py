@@ -112,6 +112,9 @@ class When2com(IntermediateModelBase):
                  only_v2i=False, attn_index="kq", renormalize=False):
         super().__init__(config, layer, in_channels, kd_flag=0, num_agent=num_agent,
                          compress_level=compress_level, only_v2i=only_v2i)
+        if self.only_v2i:
+            raise NotImplementedError("when2com under a link mask (only_v2i) is out of scope: its attention has no agreed reading "
+                                      "under a mask (DESIGN.md section 9)")
         if sparse:
             raise NotImplementedError("sparsemax attention is out of scope (DESIGN.md section 8)")
         if not has_query:
@@ -129,6 +132,16 @@ class When2com(IntermediateModelBase):
         self.key_net = KmGenerator(out_size=key_size, input_feat_sz=image_size / 32)
         self.query_net = KmGenerator(out_size=query_size, input_feat_sz=image_size / 32)
         self.attention_net = MIMOGeneralDotProductAttention(query_size, key_size, warp_flag)
+
+    def set_link_mask(self, mask):
+        """Only the all-true mask (or None) is accepted: the attention has no agreed reading under a link mask."""
+        if mask is not None:
+            m = torch.as_tensor(mask) != 0
+            A = self.agent_num
+            off = ~torch.eye(A, dtype=torch.bool).expand_as(m) if tuple(m.shape[-2:]) == (A, A) else None
+            if off is None or not bool(m[off].all()):
+                raise NotImplementedError("when2com under a link mask is out of scope (DESIGN.md section 9)")
+        self._link_mask = None
 
     def _pack(self, device):
         qk = self.query_key_net

@@ -35,9 +35,18 @@ class Conv3D(_ParamsOnly):
 class LidarEncoder(_ParamsOnly):
     """13 -> 32,32 @256^2 -> 64,64 (+1x1) @128^2 -> 128,128 (+1x1) @64^2 -> 256,256 @32^2 -> 512,512 @16^2."""
 
-    def __init__(self, height_feat_size=13):
+    def __init__(self, height_feat_size=13, compress_level=0):
         super().__init__()
+        try:
+            import operator
+            level = operator.index(compress_level)          # python and numpy integers
+        except TypeError:
+            level = -1
+        if isinstance(compress_level, bool) or not 0 <= level <= 8:
+            raise ValueError("compress_level must be an integer in 0..8, got %r" % (compress_level,))
+        compress_level = level
         self.height_feat_size = height_feat_size
+        self.compress_level = compress_level
         self.conv_pre_1 = nn.Conv2d(height_feat_size, 32, 3, 1, 1)
         self.conv_pre_2 = nn.Conv2d(32, 32, 3, 1, 1)
         self.bn_pre_1 = nn.BatchNorm2d(32)
@@ -55,6 +64,13 @@ class LidarEncoder(_ParamsOnly):
         for n, c in (("1_1", 64), ("1_2", 64), ("2_1", 128), ("2_2", 128),
                      ("3_1", 256), ("3_2", 256), ("4_1", 512), ("4_2", 512)):
             setattr(self, "bn" + n, nn.BatchNorm2d(c))
+        if compress_level > 0:
+            # upstream's communication codec on x_3: the MESSAGE is the (256 >> k)-channel map between the two
+            cc = 256 >> compress_level
+            self.com_compresser = nn.Conv2d(256, cc, kernel_size=1, stride=1)
+            self.bn_compress = nn.BatchNorm2d(cc)
+            self.com_decompresser = nn.Conv2d(cc, 256, kernel_size=1, stride=1)
+            self.bn_decompress = nn.BatchNorm2d(256)
 
     def pack(self, prefix, device):
         """-> list of ops.Layer.  Full-resolution layers carry a halo-kernel packing next to the
@@ -96,14 +112,20 @@ class LidarEncoder(_ParamsOnly):
                     c3 = self.conv3d_2
                     stage.append(ops.Layer([packing.pack_conv_bn(prefix + "conv3d_2", c3.conv3d, c3.bn3d, device=device)]))
             levels.append(stage)
+        if self.compress_level > 0:
+            # after the five stages: the codec of x_3 (run() applies it once x_4 has been computed from the uncompressed x_3)
+            levels.append(packing.pack_codec(prefix + "codec", self.com_compresser, self.bn_compress, self.com_decompresser,
+                                             self.bn_decompress, device=device))
         return levels
 
     @staticmethod
     def run(levels, x, zbits=0):
         """x: (N, X, Y, INPUT_C_PAD) bf16 NHWC, or the voxelizer's int32 bit grid (N, X, Y) with zbits height bins
-        (conv_pre_1 then expands the bits while filling its LDS patch) -> [x, x_1, x_2, x_3, x_4]."""
+        (conv_pre_1 then expands the bits while filling its LDS patch) -> [x, x_1, x_2, x_3, x_4].  compress_level > 0: x_3 is the
+        map after compress / decompress (every agent's, the ego's included), x_4 comes from the uncompressed one."""
         feats = []
-        for stage in levels:
+        codec = levels[5] if len(levels) > 5 else None
+        for stage in levels[:5]:
             k = 0
             if stage is levels[0] and len(stage) == 2 and ops.pair_eligible(stage[0].halo, stage[1].halo, x, zbits):
                 # conv_pre_1 -> conv_pre_2 in one launch, the 32-channel intermediate stays in LDS (conv_halo_pair.hip)
@@ -112,6 +134,8 @@ class LidarEncoder(_ParamsOnly):
             for layer in stage[k:]:
                 x = ops.run_layer(layer, x, zbits=zbits if x.dtype == torch.int32 else 0)
             feats.append(x)
+        if codec is not None:
+            feats[3] = ops.codec(codec, feats[3])
         return feats
 
 
@@ -317,10 +341,46 @@ class IntermediateModelBase(DetModelBase):
     def __init__(self, config, layer=3, in_channels=13, kd_flag=True, p_com_outage=0.0, num_agent=5,
                  compress_level=0, only_v2i=False):
         super().__init__(config, layer, in_channels, kd_flag, p_com_outage, num_agent, only_v2i)
-        if compress_level != 0 or only_v2i or p_com_outage != 0.0:
-            raise NotImplementedError("compress_level / only_v2i / p_com_outage are out of scope (DESIGN.md s8)")
-        self.u_encoder = LidarEncoder(in_channels)
+        if p_com_outage != 0.0:
+            raise NotImplementedError("p_com_outage is out of scope (DESIGN.md s9)")
+        from ...utils import comm
+        flags = comm.current_model_flags()      # inside `with comm.model_flags(...)`: what a constructor call that leaves the two at their defaults takes
+        if flags is not None:
+            if compress_level == 0:
+                compress_level = flags["compress_level"]
+            only_v2i = only_v2i or flags["only_v2i"]
+        self.compress_level = compress_level
+        self.only_v2i = bool(only_v2i)
+        self._link_mask = None
+        self.u_encoder = LidarEncoder(in_channels, compress_level=compress_level)
         self.decoder = LidarDecoder(in_channels)
+
+    # ---- who may talk to whom -------------------------------------------------------------
+    def set_link_mask(self, mask):
+        """mask[b, i, j] (bool, (B, A, A) or (A, A) for every frame): ego i of frame b receives from agent j.  The diagonal and the rows /
+        columns of absent agents are ignored.  None removes it.  only_v2i=True (agent 0 is the road-side unit: a link j -> i exists only if
+        i == 0 or j == 0) is ANDed with it.  Takes effect in the next make_plan(): a plan built before keeps its links."""
+        if mask is not None:
+            mask = torch.as_tensor(mask).detach().to("cpu")
+            A = self.agent_num
+            if mask.dim() not in (2, 3) or tuple(mask.shape[-2:]) != (A, A):
+                raise ValueError("link mask must be (B, %d, %d) or (%d, %d), got %s" % (A, A, A, A, tuple(mask.shape)))
+            mask = mask != 0
+        self._link_mask = mask
+
+    def links(self, batch_size):
+        """-> None when every link is allowed, else nested lists L[b][i][j] of python bools (only_v2i AND the user mask)."""
+        A = self.agent_num
+        m = self._link_mask
+        if m is None and not self.only_v2i:
+            return None
+        if m is not None and m.dim() == 3 and m.shape[0] != batch_size:
+            raise ValueError("link mask holds %d frames, the batch %d" % (m.shape[0], batch_size))
+        out = []
+        for b in range(batch_size):
+            mb = None if m is None else (m if m.dim() == 2 else m[b]).tolist()
+            out.append([[(mb is None or bool(mb[i][j])) and (not self.only_v2i or i == 0 or j == 0) for j in range(A)] for i in range(A)])
+        return out
 
     def fusion_shape(self):
         return LAYER_SHAPES[self.layer]

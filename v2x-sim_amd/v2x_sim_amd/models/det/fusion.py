@@ -30,8 +30,13 @@ class FusionBase(IntermediateModelBase):
         A = self.agent_num
         counts, items, rows = self.frame_plan(num_agent_tensor, batch_size, A)
         coef = torch.zeros((len(items), A), dtype=torch.float32)
+        L = self.links(batch_size)
         for m, (a, f) in enumerate(items):
             coef[m, :counts[f]] = 1.0        # ego included
+            if L is not None:                # link mask: the fusion list is the ego and the linked neighbours (mean divides by its length)
+                for j in range(counts[f]):
+                    if j != a and not L[f][a][j]:
+                        coef[m, j] = 0.0
         full = len(items) == A * batch_size
         return {"items": ops.items_tensor(items, A, batch_size, device), "coef": coef.to(device),
                 "rows": None if full else torch.tensor(rows, device=device)}

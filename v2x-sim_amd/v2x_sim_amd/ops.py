@@ -370,6 +370,61 @@ def conv2d(pc, in0, in1=None, out=None, out_coff=0, split=0, zbits=0, splitk=0):
     return (out, out2) if split else out
 
 
+# ------------------------------------------------------------------ communication codec (compress_level; codec.hip)
+class PackedCodec:
+    """Device-resident packed parameters of the compress / decompress pair (packing.pack_codec): `weight` = the MFMA fragments of both
+    matrices (include/v2x_amd.h), `ss` = their folded scales and shifts."""
+
+    __slots__ = ("name", "C", "Cc", "weight", "ss")
+
+    def __init__(self, name, C, Cc, weight, ss):
+        self.name, self.C, self.Cc, self.weight, self.ss = name, C, Cc, weight, ss
+
+
+def _codec_rows(pc, t, channels, what):
+    if t.shape[-1] != channels:
+        raise ValueError("%s: %s has %d channels, expected %d" % (pc.name, what, t.shape[-1], channels))
+    return t.numel() // channels
+
+
+def codec(pc, x, want_msg=False):
+    """x (..., C) bf16 NHWC -> y of the same shape: relu(bn_d(Wd relu(bn_c(Wc x)))) in one launch, the Cc-channel message kept in registers.
+    want_msg: -> (y, msg (..., Cc) bf16), the message an agent would send (natural channel order)."""
+    M = _codec_rows(pc, x, pc.C, "x")
+    y = torch.empty_like(x)
+    msg = torch.empty(tuple(x.shape[:-1]) + (pc.Cc,), dtype=torch.bfloat16, device=x.device) if want_msg else None
+    prof = _Prof("codec_kernel<%d, %d, fused>" % (pc.C, pc.Cc), 4.0 * M * pc.C * pc.Cc, M * (4 * pc.C + (2 * pc.Cc if want_msg else 0)), pc.name)
+    rc = _lib.load().v2x_codec_1x1(_dev(x, torch.bfloat16, "x"), M, pc.C, pc.Cc, _dev(pc.weight, torch.bfloat16, "weight"), _dev(pc.ss, torch.float32, "ss"),
+                                   _dev(y, torch.bfloat16, "y"), _dev_opt(msg, torch.bfloat16, "msg"), _stream())
+    prof.done()
+    _lib.check(rc, "v2x_codec_1x1(%s)" % pc.name)
+    return (y, msg) if want_msg else y
+
+
+def codec_compress(pc, x):
+    """The sender's half: x (..., C) bf16 -> msg (..., Cc) bf16."""
+    M = _codec_rows(pc, x, pc.C, "x")
+    msg = torch.empty(tuple(x.shape[:-1]) + (pc.Cc,), dtype=torch.bfloat16, device=x.device)
+    prof = _Prof("codec_kernel<%d, %d, compress>" % (pc.C, pc.Cc), 2.0 * M * pc.C * pc.Cc, M * 2 * (pc.C + pc.Cc), pc.name)
+    rc = _lib.load().v2x_codec_compress(_dev(x, torch.bfloat16, "x"), M, pc.C, pc.Cc, _dev(pc.weight, torch.bfloat16, "weight"),
+                                        _dev(pc.ss, torch.float32, "ss"), _dev(msg, torch.bfloat16, "msg"), _stream())
+    prof.done()
+    _lib.check(rc, "v2x_codec_compress(%s)" % pc.name)
+    return msg
+
+
+def codec_decompress(pc, msg):
+    """The receiver's half: msg (..., Cc) bf16 -> y (..., C) bf16; codec_decompress(codec_compress(x)) is bit-identical to codec(x)."""
+    M = _codec_rows(pc, msg, pc.Cc, "msg")
+    y = torch.empty(tuple(msg.shape[:-1]) + (pc.C,), dtype=torch.bfloat16, device=msg.device)
+    prof = _Prof("codec_kernel<%d, %d, decompress>" % (pc.C, pc.Cc), 2.0 * M * pc.C * pc.Cc, M * 2 * (pc.C + pc.Cc), pc.name)
+    rc = _lib.load().v2x_codec_decompress(_dev(msg, torch.bfloat16, "msg"), M, pc.C, pc.Cc, _dev(pc.weight, torch.bfloat16, "weight"),
+                                          _dev(pc.ss, torch.float32, "ss"), _dev(y, torch.bfloat16, "y"), _stream())
+    prof.done()
+    _lib.check(rc, "v2x_codec_decompress(%s)" % pc.name)
+    return y
+
+
 def _pair_desc(pc, N, H, W):
     d = ConvDesc()
     d.C0, d.C1, d.up0 = pc.C0, pc.C1, pc.up0

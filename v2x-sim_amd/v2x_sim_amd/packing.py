@@ -168,6 +168,42 @@ def pack_conv_bn(name, conv, bn, *, relu=True, epilogue=V2X_EPI_BF16, device="cu
                      epilogue=epilogue, device=device, **kw)
 
 
+def codec_slot_channel(chunk, q, e):
+    """The K-slot map of the codec's packed decompress weights (include/v2x_amd.h): element e = 4 h + r of lane quarter q in K chunk `chunk`
+    multiplies compressed channel 32 chunk + 16 h + 4 q + r -- the channel the lane's stage-one accumulator r of tile 2 chunk + h holds."""
+    return 32 * chunk + 16 * (e >> 2) + 4 * q + (e & 3)
+
+
+def pack_codec_host(C, Cc, wc, scale_c, shift_c, wd, scale_d, shift_d):
+    """fp32 CPU tensors wc [Cc, C], wd [C, Cc] and the folded scales / shifts -> (weight uint16-as-bf16 [elems], ss fp32) CPU tensors in the
+    layout v2x_codec_* read (v2x_pack_codec)."""
+    import ctypes as C_
+    import numpy as np
+    lib = _lib.load()
+    n_ss = C_.c_longlong(0)
+    n_w = lib.v2x_pack_codec_size(C, Cc, C_.byref(n_ss))
+    if n_w < 0:
+        _lib.check(int(n_w), "v2x_pack_codec_size")
+    f = lambda t: np.ascontiguousarray(t.detach().float().cpu().numpy())   # noqa: E731
+    a = [f(wc).reshape(Cc, C), f(scale_c), f(shift_c), f(wd).reshape(C, Cc), f(scale_d), f(shift_d)]
+    w, ss = np.empty(n_w, np.uint16), np.empty(n_ss.value, np.float32)
+    p = lambda x: x.ctypes.data_as(C_.c_void_p)   # noqa: E731
+    _lib.check(lib.v2x_pack_codec(C, Cc, *[p(x) for x in a], p(w), p(ss)), "v2x_pack_codec")
+    return torch.from_numpy(w.view(np.int16)).view(torch.bfloat16), torch.from_numpy(ss)
+
+
+def pack_codec(name, conv_c, bn_c, conv_d, bn_d, device="cuda"):
+    """com_compresser / bn_compress / com_decompresser / bn_decompress (eval-mode BN folded) -> ops.PackedCodec on `device`."""
+    from .ops import PackedCodec
+    Cc, C = conv_c.out_channels, conv_c.in_channels
+    if (conv_d.in_channels, conv_d.out_channels) != (Cc, C) or conv_c.kernel_size != (1, 1) or conv_d.kernel_size != (1, 1):
+        raise ValueError("%s: a codec is a 1x1 C -> Cc -> C pair" % name)
+    s1, t1 = fold_bn(conv_c.bias, bn_c, Cc)
+    s2, t2 = fold_bn(conv_d.bias, bn_d, C)
+    w, ss = pack_codec_host(C, Cc, conv_c.weight, s1, t1, conv_d.weight, s2, t2)
+    return PackedCodec(name, C, Cc, w.to(device).contiguous(), ss.to(device).contiguous())
+
+
 def pack_linear(name, lin, *, relu, epilogue=V2X_EPI_BF16, col_perm=None, device="cuda"):
     """nn.Linear as a 1x1 conv on a 1x1 map.  col_perm re-orders input features (NCHW -> NHWC flatten)."""
     w = lin.weight.detach().float().cpu()

@@ -41,8 +41,9 @@ class AgentShard:
         self.rows = list(range(self.lo, self.hi))
         self.items = [(r // total_frames, r % total_frames) for r in self.rows]  # (agent, frame)
 
-    def fusion_plan(self, num_agent_tensor, device):
-        """items / coef of the maps this rank fuses (real agents only) + their local row index."""
+    def fusion_plan(self, num_agent_tensor, device, links=None):
+        """items / coef of the maps this rank fuses (real agents only) + their local row index.  links: the model's link mask
+        (IntermediateModelBase.links(Bt): L[f][ego][source], None = every link), identical on every rank."""
         nat = num_agent_tensor.detach().to("cpu") if isinstance(num_agent_tensor, torch.Tensor) else num_agent_tensor
         counts = [int(nat[f][0]) for f in range(self.Bt)]
         if min(counts) < 2:
@@ -51,12 +52,15 @@ class AgentShard:
         for local, (a, f) in enumerate(self.items):
             if a < counts[f]:
                 sel.append(local)
-                coef.append([1.0 if (j != a and j < counts[f]) else 0.0 for j in range(self.A)])
+                coef.append([1.0 if (j != a and j < counts[f] and (links is None or links[f][a][j])) else 0.0 for j in range(self.A)])
+                if not any(coef[-1]):
+                    raise RuntimeError("V2VNet needs >= 1 linked neighbour for every ego (stack expects a non-empty TensorList): "
+                                       "agent %d of frame %d has none under the link mask" % (a, f))
         items = [self.items[i] for i in sel]
         full = len(sel) == self.per_rank
         return {"items": ops.items_tensor(items, self.A, self.Bt, device),
                 "coef": torch.tensor(coef, dtype=torch.float32, device=device).view(-1, self.A),
-                "local_rows": None if full else torch.tensor(sel, device=device), "n": len(sel)}
+                "local_rows": None if full else torch.tensor(sel, device=device), "n": len(sel), "links": links}
 
 
 def exchange_features(local_feat, world, group=None, out=None):
@@ -222,6 +226,10 @@ class ShardedV2VNet:
 
     def fuse_local(self, feats, trans, plan, pk, gathered0=None):
         m, sh = self.model, self.shard
+        want = m.links(sh.Bt) if hasattr(m, "links") else None
+        if want is not None and plan.get("links") != want:
+            # a masked / only_v2i model must never fuse over a plan built for other links (fusion_plan(..., links=model.links(Bt)))
+            raise ValueError("the fusion plan was not built for this model's link mask: pass links=model.links(Bt) to AgentShard.fusion_plan")
         local = feats[m.layer]
         cur = local
         if gathered0 is None:

@@ -62,7 +62,15 @@ def encoder(e, x):
     x_2 = _conv3d_1x1(_cbr(x_2, e.conv2_2, e.bn2_2), e.conv3d_2)
     x_3 = _cbr(_cbr(x_2, e.conv3_1, e.bn3_1), e.conv3_2, e.bn3_2)
     x_4 = _cbr(_cbr(x_3, e.conv4_1, e.bn4_1), e.conv4_2, e.bn4_2)
+    if getattr(e, "compress_level", 0) > 0:     # the communication codec: on x_3, after x_4 has been computed from the uncompressed map
+        x_3 = _cbr(_cbr(x_3, e.com_compresser, e.bn_compress), e.com_decompresser, e.bn_decompress)
     return [x, x_1, x_2, x_3, x_4]
+
+
+def _links(model, B):
+    """The model's link mask as a hashable nested tuple L[f][ego][source] (None: every link)."""
+    L = model.links(B) if hasattr(model, "links") else None
+    return None if L is None else tuple(tuple(tuple(r) for r in fr) for fr in L)
 
 
 def decoder(d, x, x_1, x_2, x_3, x_4):
@@ -167,10 +175,17 @@ def v2v_fuse(model, feat, trans, num_agent_tensor, B, gru_conv=None):
     # the plan's index tensors are cached per (agent table, B, device): building them is a host -> device copy, which must not happen
     # inside a hipGraph capture (train/graph_step.py captures the step after warm-up calls have filled this cache)
     A1, A2 = trans.shape[1], trans.shape[2]
-    key = (tuple(counts), B, A, A1, A2, str(dev), str(feat.dtype))
+    L = _links(model, B)
+    key = (tuple(counts), B, A, A1, A2, str(dev), str(feat.dtype), L)
     cache = model.__dict__.setdefault("_v2v_plan_cache", {})
+    # linked neighbours per ego item (host arithmetic; = the frame's agent count - 1 without a link mask)
+    n_nb = [sum(1 for j in range(counts[f]) if j != a and (L is None or L[f][a][j])) for (a, f) in items]
+    if min(n_nb) < 1:
+        raise RuntimeError("V2VNet needs >= 1 linked neighbour for every ego (stack expects a non-empty TensorList): "
+                           "agent %d of frame %d has none under the link mask" % items[n_nb.index(0)])
+    uniform = n_nb[0] if min(n_nb) == max(n_nb) else 0
     if key not in cache:
-        pairs = [(m, j * B + f, f, a, j) for m, (a, f) in enumerate(items) for j in range(counts[f]) if j != a]
+        pairs = [(m, j * B + f, f, a, j) for m, (a, f) in enumerate(items) for j in range(counts[f]) if j != a and (L is None or L[f][a][j])]
         cache.clear()
         # inv[r] = the pairs that read row r of the maps, in pair order -- defined when every row is read equally often (every frame full)
         uses = {}
@@ -182,7 +197,7 @@ def v2v_fuse(model, feat, trans, num_agent_tensor, B, gru_conv=None):
             inv = torch.tensor([uses[r] for r in range(feat.shape[0])], device=dev)
         cache[key] = (torch.tensor([p[1] for p in pairs], device=dev), torch.tensor([p[0] for p in pairs], device=dev),
                       torch.tensor([(f * A1 + a) * A2 + j for (_, _, f, a, j) in pairs], device=dev),
-                      torch.tensor([counts[f] - 1 for (_, f) in items], device=dev, dtype=feat.dtype).view(-1, 1, 1, 1),
+                      torch.tensor(n_nb, device=dev, dtype=feat.dtype).view(-1, 1, 1, 1),
                       torch.tensor(rows, device=dev), inv)
     src, dst, tsel, cnt, rows_t, inv = cache[key]
     Tp = trans.reshape(-1, 4, 4).index_select(0, tsel).to(feat.dtype)        # trans[f, a, j] of every (ego item, neighbour) pair
@@ -190,10 +205,10 @@ def v2v_fuse(model, feat, trans, num_agent_tensor, B, gru_conv=None):
     for _ in range(model.gnn_rounds()):
         base = cur if model.neighbor_source == "updated" else feat
         warped = warp_batch(_GatherRowsDup.apply(base, src, inv) if inv is not None else base.index_select(0, src), Tp)
-        if min(counts) == max(counts):
-            # every frame has the same number of agents: the pairs of an ego item are consecutive (see `pairs`), so the mean over its neighbours is
-            # a reduction over a dense axis -- one deterministic kernel instead of zeros + index_add_ (atomic adds) + a division
-            mean = warped.view((len(items), counts[0] - 1) + tuple(feat.shape[1:])).mean(1)
+        if uniform:
+            # every ego has the same number of (linked) neighbours: the pairs of an ego item are consecutive (see `pairs`), so the mean over its
+            # neighbours is a reduction over a dense axis -- one deterministic kernel instead of zeros + index_add_ (atomic adds) + a division
+            mean = warped.view((len(items), uniform) + tuple(feat.shape[1:])).mean(1)
         else:
             mean = torch.zeros((len(items),) + tuple(feat.shape[1:]), device=dev, dtype=feat.dtype).index_add_(0, dst, warped) / cnt
         h = _gru_step(model.convgru, torch.cat([cur.index_select(0, rows_t), mean], 1), gru_conv)
@@ -206,6 +221,8 @@ def when2com_fuse(model, x, feat, trans, num_agent_tensor, B, training=True, inf
     softmax over the keys; training uses the soft scores, inference 'activated' / 'argmax_test' as the HIP path.
     x (A*B, Z, X, Y) input, feat (A*B, C, H, W) fusion-layer maps -> fused maps (zeros for padding agents)."""
     A = model.agent_num
+    if _links(model, B) is not None:
+        raise NotImplementedError("when2com under a link mask is out of scope (DESIGN.md section 9)")
     qk = model.query_key_net
     y = encoder(qk.lidar_encoder, x)[4]
     for i in range(1, 6):
@@ -246,7 +263,8 @@ def _ego_views(model, feat, trans, num_agent_tensor, B):
     A = model.agent_num
     counts, items, rows = model.frame_plan(num_agent_tensor, B, A)
     dev = feat.device
-    pairs = [(m, k * B + f, f, q, k) for m, (q, f) in enumerate(items) for k in range(counts[f])]
+    L = _links(model, B)             # the fusion list of an ego: itself and its linked neighbours
+    pairs = [(m, k * B + f, f, q, k) for m, (q, f) in enumerate(items) for k in range(counts[f]) if k == q or L is None or L[f][q][k]]
     src = torch.tensor([p[1] for p in pairs], device=dev)
     dst = torch.tensor([p[0] for p in pairs], device=dev)
     Tp = torch.stack([trans[f, q, k] for (_, _, f, q, k) in pairs]).to(feat.dtype)
@@ -261,7 +279,7 @@ def simple_fuse(model, feat, trans, num_agent_tensor, B):
     """Sum / Mean / Max / Cat fusion (upstream {Sum,Mean,Max,Cat}Fusion.py on FusionBase.py): reduce [ego map, warped
     neighbour maps] per ego; CatFusion = ModulationLayer3(cat(ego, mean))."""
     from .._lib import V2X_FUSE_MAX, V2X_FUSE_MEAN, V2X_FUSE_WSUM
-    val, dst, own, items, rows, counts, _ = _ego_views(model, feat, trans, num_agent_tensor, B)
+    val, dst, own, items, rows, counts, pairs = _ego_views(model, feat, trans, num_agent_tensor, B)
     n = len(items)
     shape = (n,) + tuple(feat.shape[1:])
     mode = model.FUSE_MODE
@@ -271,7 +289,10 @@ def simple_fuse(model, feat, trans, num_agent_tensor, B):
     else:
         fused = torch.zeros(shape, device=feat.device, dtype=feat.dtype).index_add(0, dst, val)
         if mode == V2X_FUSE_MEAN:
-            cnt = torch.tensor([counts[f] for (_, f) in items], device=feat.device, dtype=feat.dtype).view(-1, 1, 1, 1)
+            n_src = [0] * n          # the length of each ego's fusion list (= the frame's agent count without a link mask)
+            for p in pairs:
+                n_src[p[0]] += 1
+            cnt = torch.tensor(n_src, device=feat.device, dtype=feat.dtype).view(-1, 1, 1, 1)
             fused = fused / cnt
         elif mode != V2X_FUSE_WSUM:
             raise ValueError("unknown fusion mode")

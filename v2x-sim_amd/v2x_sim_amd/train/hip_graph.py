@@ -479,7 +479,49 @@ def encoder(e, x):
     x_2 = conv3d_1x1(cbr(x_2, e.conv2_2, e.bn2_2), e.conv3d_2)
     x_3 = cbr(cbr(x_2, e.conv3_1, e.bn3_1), e.conv3_2, e.bn3_2)
     x_4 = cbr(cbr(x_3, e.conv4_1, e.bn4_1), e.conv4_2, e.bn4_2)
+    if getattr(e, "compress_level", 0) > 0:     # the communication codec: on x_3, after x_4 has been computed from the uncompressed map
+        x_3 = codec(e, x_3)
     return [x, x_1, x_2, x_3, x_4]
+
+
+_CODEC_WARNED = set()
+
+
+def _cbr_1x1_torch(x, conv, bn):
+    """1x1 conv + batch-statistics BN + ReLU with library ops (fp32 F.linear / F.batch_norm) on a bf16 NHWC map: the layers of the codec whose
+    channel count the kernels do not take."""
+    if not bn.training:
+        raise RuntimeError("hip_graph is the TRAINING graph (batch statistics); evaluation runs the inference engine")
+    y = F.linear(x.float(), conv.weight.reshape(conv.weight.shape[0], conv.weight.shape[1]), conv.bias)
+    if bn.track_running_stats and bn.num_batches_tracked is not None:
+        if _DEFER_COUNTERS[0]:
+            _PENDING_COUNTERS.append(bn.num_batches_tracked)
+        else:
+            bn.num_batches_tracked += 1
+    if bn.momentum is None:
+        raise NotImplementedError("cumulative-average BatchNorm (momentum=None)")
+    c = y.shape[-1]
+    y = F.batch_norm(y.reshape(-1, c), bn.running_mean if bn.track_running_stats else None, bn.running_var if bn.track_running_stats else None,
+                     bn.weight, bn.bias, True, bn.momentum, bn.eps).reshape(y.shape)
+    return F.relu(y).to(BF16)
+
+
+def codec(e, x_3):
+    """com_compresser / bn_compress / ReLU / com_decompresser / bn_decompress / ReLU with batch statistics.  Cc = 256 >> k >= 32 (k <= 3): both
+    layers on the kernels (_Conv1x1 + bn_train, like conv3d_1 / conv3d_2).  Cc < 32: the 1x1 kernels want a multiple of 32 input channels
+    and the BatchNorm kernel >= 8 channels, so both layers run on the library ops -- said once per shape, never silently."""
+    cc = e.com_compresser.out_channels
+    N, H, W, _ = x_3.shape
+    if cc % 32 == 0 and H % 8 == 0 and W % 32 == 0:
+        m = bn_relu(conv1x1(x_3, e.com_compresser.weight, e.com_compresser.bias), e.bn_compress)
+        return bn_relu(conv1x1(m, e.com_decompresser.weight, e.com_decompresser.bias), e.bn_decompress)
+    key = (cc, H, W)
+    if key not in _CODEC_WARNED:
+        _CODEC_WARNED.add(key)
+        import warnings
+        warnings.warn("hip_graph: the codec's %d-channel message on %d x %d maps does not fit the training kernels (1x1: Cin %% 32 == 0, H %% 8 == 0, "
+                      "W %% 32 == 0); its two layers train on the library GEMM / BatchNorm" % (cc, H, W))
+    return _cbr_1x1_torch(_cbr_1x1_torch(x_3, e.com_compresser, e.bn_compress), e.com_decompresser, e.bn_decompress)
 
 
 def decoder(d, x, x_1, x_2, x_3, x_4):
@@ -591,7 +633,9 @@ def _v2v_plan(model, counts, items, rows, B, A, trans, N, device):
 def v2v_fuse_nhwc(model, feat, trans, num_agent_tensor, B):
     """V2VNet's message-passing rounds on the bf16 NHWC fusion-layer maps feat (A*B, H, W, C): per round a message launch, the ConvGRU's input convolution and
     a gates launch (TRAIN_V2V_NHWC 1).  -> the updated maps, or None when this form does not cover the batch (a frame with fewer agents than another, a
-    channel count or extent the kernels do not tile): the caller then runs graph.v2v_fuse on the fp32 graph."""
+    channel count or extent the kernels do not tile; a link mask that removes ANY link -- also a uniform one such as a ring, which the message
+    kernel could take: its plan is built for every neighbour of a frame, so every masked case is left to the fp32 stage): the caller then runs
+    graph.v2v_fuse on the fp32 graph."""
     if tuning.get("TRAIN_V2V_NHWC") == 0 or feat.dtype != BF16 or trans is None:
         return None
     g = model.convgru
@@ -601,6 +645,9 @@ def v2v_fuse_nhwc(model, feat, trans, num_agent_tensor, B):
     if min(counts) < 2:
         raise RuntimeError("V2VNet needs >= 2 agents in every frame (stack expects a non-empty TensorList)")
     w = g.weight_ih_l0
+    L = model.links(B) if hasattr(model, "links") else None
+    if L is not None and any(not L[f][a][j] for (a, f) in items for j in range(counts[f]) if j != a):
+        return None          # a link mask that removes a link: the message kernel's plan has every neighbour of a frame -> the fp32 stage (as a ragged batch)
     if min(counts) != max(counts) or tuple(w.shape) != (3 * C, 2 * C, 3, 3) or C % 32 or not hip_eligible(w, 1, H, W) or not ops.gru_gates_nhwc_ok(N * H * W, C) \
             or g.bias_ih_l0 is None or g.bias_hh_l0 is None:
         return None
