@@ -15,7 +15,7 @@
 // Determinism: a workgroup owns a contiguous run of pixels and writes ONE partial per channel; the finish kernels add the partials
 // in a fixed order in fp64.  No atomics anywhere, so two runs give the same bits (MIOpen's BN backward does not promise that).
 // var = E[x^2] - mean^2 is formed in fp64 from the fp32 partials (a thread adds at most M * C / (8 * 256 * n_blocks) values per channel).
-#include "common.h"
+#include "train_math.h"
 
 constexpr int BN_THREADS = 256;
 constexpr int BN_MAX_BLOCKS = 2048;
@@ -37,15 +37,6 @@ struct BnArgs {
     int relu;
     int partial_t;         // layout of `partial`: 1 = [kind][channel][workgroup] (round 6), 0 = [workgroup][kind][channel]
 };
-
-__device__ __forceinline__ void unpack8(const uint4 v, float f[8]) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(w[i] << 16);
-        f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-}
 
 // MODE 0: sum x, sum x^2.   MODE 1: sum g, sum g * xhat with g = dy masked by the recomputed ReLU.
 template <int MODE>
@@ -75,7 +66,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_partial_kernel(const BnArgs a) 
     const uint4 *dv = reinterpret_cast<const uint4 *>(a.dy);
     for (long long v = v0 + t; v < v1; v += BN_THREADS) {
         float x[8];
-        unpack8(xv[v], x);
+        tm_unpack8(xv[v], x);
         if (MODE == 0) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -84,7 +75,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_partial_kernel(const BnArgs a) 
             }
         } else {
             float d[8];
-            unpack8(dv[v], d);
+            tm_unpack8(dv[v], d);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const float xh = (x[i] - mu[i]) * is[i];
@@ -199,19 +190,19 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const BnArgs a) {
     uint4 *yv = reinterpret_cast<uint4 *>(a.out);
     for (long long v = (long long)blockIdx.x * BN_THREADS + t; v < total; v += (long long)gridDim.x * BN_THREADS) {
         float x[8];
-        unpack8(xv[v], x);
+        tm_unpack8(xv[v], x);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             x[i] = fmaf(x[i], sc[i], sh[i]);
             if (a.relu) x[i] = fmaxf(x[i], 0.f);
         }
-        yv[v] = make_uint4(pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3]), pack_bf16x2(x[4], x[5]), pack_bf16x2(x[6], x[7]));
+        yv[v] = tm_pack8(x);
     }
 }
 
 // SUM: also the per-channel sum of the dx values AS STORED (bf16-rounded) -- the bias gradient of the convolution that produced x
 // (db = sum over pixels of dx; upstream: autograd's reduction in nn.Conv2d.backward), one partial per workgroup and channel in
-// a.partial[blockIdx.x][C] (the finish kernel of the channel sum adds them in workgroup order): saves the separate read of dx
+// a.partial[C][gridDim.x] (channel_sum_finish_kernel adds them in workgroup order): saves the separate read of dx
 template <bool SUM>
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(const BnArgs a) {
     __shared__ float red[SUM ? BN_THREADS : 1][9];
@@ -236,8 +227,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(const BnArgs a
     uint4 *ov = reinterpret_cast<uint4 *>(a.out);
     for (long long v = (long long)blockIdx.x * BN_THREADS + t; v < total; v += (long long)gridDim.x * BN_THREADS) {
         float x[8], d[8];
-        unpack8(xv[v], x);
-        unpack8(dv[v], d);
+        tm_unpack8(xv[v], x);
+        tm_unpack8(dv[v], d);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const float xh = (x[i] - mu[i]) * is[i];
@@ -245,13 +236,10 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(const BnArgs a
             const float gr = (a.relu && !(y > 0.f)) ? 0.f : d[i];
             x[i] = ga[i] * is[i] * (gr - k0[i] - xh * k1[i]);
         }
-        const uint4 o = make_uint4(pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3]), pack_bf16x2(x[4], x[5]), pack_bf16x2(x[6], x[7]));
+        const uint4 o = tm_pack8(x);
         ov[v] = o;
         if (SUM) {
-            float r[8];
-            unpack8(o, r);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[i] += r[i];
+            tm_acc8(acc, o);
         }
     }
     if (SUM) {
@@ -283,16 +271,19 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(const BnArgs a
     }
 }
 
-// one wave per channel over the channel-major partials of bn_bwd_apply_kernel<true>: lane l adds entries l, l + 64, ... (fp64), fixed butterfly
-__global__ __launch_bounds__(256) void bn_dxsum_finish_kernel(const float *__restrict__ part, int nblk, int C, float *__restrict__ out) {
+// out[c] = the sum of channel c's per-workgroup partials part[b * bstride + c * cstride], b < nblk -- [workgroup][C] partials (channel_sum_partial_kernel,
+// cast_pad_chsum_kernel): (C, 1); channel-major [C][workgroups] (bn_bwd_apply_kernel<true>): (1, nblk).  One wave per channel: lane l adds the partials
+// l, l + 64, ... in order (fp64), then a fixed butterfly over the 64 lanes -- a fixed tree, bit-reproducible (one THREAD per channel walking up to 1 024
+// partials was 72 us per call: dependent loads)
+__global__ __launch_bounds__(256) void channel_sum_finish_kernel(const float *__restrict__ part, int nblk, int C, size_t bstride, size_t cstride, float *__restrict__ out) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= C) return;
-    const float *p = part + (size_t)c * nblk;
+    const float *p = part + c * cstride;
     double s = 0.0;
     for (int b0 = lane; b0 < nblk; b0 += 64 * 8) {        // eight loads in flight, added in index order
         float v[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = (b0 + 64 * k < nblk) ? p[b0 + 64 * k] : 0.f;
+        for (int k = 0; k < 8; ++k) v[k] = (b0 + 64 * k < nblk) ? p[(b0 + 64 * k) * bstride] : 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) s += (double)v[k];
     }
@@ -317,10 +308,8 @@ static int bn_plan(long long M, int C, BnArgs &a) {
     return a.n_blocks;
 }
 
-static bool bn_shape_ok(long long M, int C) { return M > 0 && C >= 8 && C % 8 == 0 && BN_THREADS % (C / 8) == 0; }
-
 extern "C" long long v2x_bn_train_workspace_size(long long M, int C) {
-    if (!bn_shape_ok(M, C)) return 0;
+    if (!tm_chan8_shape_ok(M, C)) return 0;
     BnArgs a;
     return (long long)bn_plan(M, C, a) * 2 * C * (long long)sizeof(float);
 }
@@ -329,7 +318,7 @@ extern "C" int v2x_bn_train_forward(const uint16_t *x, long long M, int C, const
                                     float momentum, float *running_mean, float *running_var, int relu, uint16_t *y,
                                     float *save_mean, float *save_invstd, float *workspace, v2x_stream_t stream) {
     V2X_REQUIRE(x && gamma && beta && y && save_mean && save_invstd && workspace, "v2x_bn_train_forward: null pointer");
-    V2X_REQUIRE(bn_shape_ok(M, C), "v2x_bn_train_forward: needs M > 0 and C in {8, 16, 32, ..., 2048} (C / 8 divides 256), got M=%lld C=%d", M, C);
+    V2X_REQUIRE(tm_chan8_shape_ok(M, C), "v2x_bn_train_forward: needs M > 0 and C in {8, 16, 32, ..., 2048} (C / 8 divides 256), got M=%lld C=%d", M, C);
     V2X_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "v2x_bn_train_forward: running_mean and running_var go together");
     BnArgs a = {};
     bn_plan(M, C, a);
@@ -362,7 +351,7 @@ static int bn_train_backward_impl(const uint16_t *x, const uint16_t *dy, long lo
                                   const float *save_mean, const float *save_invstd, int relu, uint16_t *dx, float *dgamma,
                                   float *dbeta, float *workspace, float *dx_sum, float *sum_workspace, v2x_stream_t stream) {
     V2X_REQUIRE(x && dy && gamma && beta && save_mean && save_invstd && dx && dgamma && dbeta && workspace, "v2x_bn_train_backward: null pointer");
-    V2X_REQUIRE(bn_shape_ok(M, C), "v2x_bn_train_backward: needs M > 0 and C in {8, 16, 32, ..., 2048} (C / 8 divides 256), got M=%lld C=%d", M, C);
+    V2X_REQUIRE(tm_chan8_shape_ok(M, C), "v2x_bn_train_backward: needs M > 0 and C in {8, 16, 32, ..., 2048} (C / 8 divides 256), got M=%lld C=%d", M, C);
     BnArgs a = {};
     bn_plan(M, C, a);
     a.x = x;
@@ -385,7 +374,7 @@ static int bn_train_backward_impl(const uint16_t *x, const uint16_t *dy, long lo
         if (blocks > BN_DXSUM_MAX_BLOCKS) blocks = BN_DXSUM_MAX_BLOCKS;
         a.partial = sum_workspace;                 // the statistics' partials (workspace) are consumed by the finish kernel above
         hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3((unsigned)blocks), dim3(BN_THREADS), 0, s, a);
-        hipLaunchKernelGGL(bn_dxsum_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, s, sum_workspace, (int)blocks, C, dx_sum);
+        hipLaunchKernelGGL(channel_sum_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, s, sum_workspace, (int)blocks, C, (size_t)1, (size_t)blocks, dx_sum);
     } else {
         if (blocks > 8192) blocks = 8192;
         hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3((unsigned)blocks), dim3(BN_THREADS), 0, s, a);
@@ -401,7 +390,7 @@ extern "C" int v2x_bn_train_backward(const uint16_t *x, const uint16_t *dy, long
 }
 
 extern "C" long long v2x_bn_dxsum_workspace_size(long long M, int C) {
-    if (!bn_shape_ok(M, C)) return 0;
+    if (!tm_chan8_shape_ok(M, C)) return 0;
     long long blocks = (M * (C / 8) + BN_THREADS - 1) / BN_THREADS;
     if (blocks > BN_DXSUM_MAX_BLOCKS) blocks = BN_DXSUM_MAX_BLOCKS;
     return blocks * C * (long long)sizeof(float);
@@ -428,53 +417,20 @@ static int cs_blocks(long long M, int C) {
 }
 
 __global__ __launch_bounds__(256) void channel_sum_partial_kernel(const uint16_t *__restrict__ x, long long M, int C, float *__restrict__ part) {
-    __shared__ float red[256][8];
     const int groups = C / 8, rpp = 256 / groups;
     const int cg = threadIdx.x % groups, r0 = threadIdx.x / groups;
     const long long per = (M + gridDim.x - 1) / gridDim.x;
     const long long lo = (long long)blockIdx.x * per, hi = lo + per < M ? lo + per : M;
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (long long r = lo + r0; r < hi; r += rpp) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(x + r * C + cg * 8);
-        const uint32_t wds[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] += bf16_to_f32((uint16_t)(wds[j >> 1] >> ((j & 1) * 16)));
+        tm_acc8(acc, *reinterpret_cast<const uint4 *>(x + r * C + cg * 8));
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[threadIdx.x][j] = acc[j];
-    __syncthreads();
-    if (r0 == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float s = 0.f;
-            for (int k = 0; k < rpp; ++k) s += red[k * groups + cg][j];
-            part[(size_t)blockIdx.x * C + cg * 8 + j] = s;
-        }
-    }
-}
-
-// one wave per channel: lane l adds the partials l, l + 64, ... in order (fp64), then a fixed butterfly over the 64 lanes -- a fixed tree,
-// bit-reproducible (one THREAD per channel walking up to 1 024 partials was 72 us per call: dependent loads)
-__global__ __launch_bounds__(256) void channel_sum_finish_kernel(const float *__restrict__ part, int nblk, int C, float *__restrict__ out) {
-    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (c >= C) return;
-    double s = 0.0;
-    for (int b0 = lane; b0 < nblk; b0 += 64 * 8) {        // eight loads in flight, added in index order
-        float v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = (b0 + 64 * k < nblk) ? part[(size_t)(b0 + 64 * k) * C + c] : 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += (double)v[k];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if (lane == 0) out[c] = (float)s;
+    tm_channel_partials(acc, groups, rpp, cg, r0, C, part);
 }
 
 // fp32 [M][C] -> bf16 [M][Cp] (zero-padded channels) + per-workgroup partial channel sums of the fp32 values: the logit gradients of a 1x1 head on their way
 // into the data- / weight-gradient kernels (include/v2x_amd.h: v2x_cast_pad_chsum_f32).  A thread owns one 8-channel group of the padded row (one 16-B store).
 __global__ __launch_bounds__(256) void cast_pad_chsum_kernel(const float *__restrict__ x, long long M, int C, int Cp, uint16_t *__restrict__ out, float *__restrict__ part) {
-    __shared__ float red[256][8];
     const int groups = Cp / 8, rpp = 256 / groups;
     const int cg = threadIdx.x % groups, r0 = threadIdx.x / groups;
     const long long per = (M + gridDim.x - 1) / gridDim.x;
@@ -485,39 +441,25 @@ __global__ __launch_bounds__(256) void cast_pad_chsum_kernel(const float *__rest
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
         if (q0) a = *reinterpret_cast<const float4 *>(x + r * C + cg * 8);
         if (q1) b = *reinterpret_cast<const float4 *>(x + r * C + cg * 8 + 4);
-        acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
-        acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
-        uint4 v;
-        v.x = pack_bf16x2(a.x, a.y);
-        v.y = pack_bf16x2(a.z, a.w);
-        v.z = pack_bf16x2(b.x, b.y);
-        v.w = pack_bf16x2(b.z, b.w);
-        *reinterpret_cast<uint4 *>(out + r * Cp + cg * 8) = v;
-    }
+        const float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
-    for (int j = 0; j < 8; ++j) red[threadIdx.x][j] = acc[j];
-    __syncthreads();
-    if (r0 == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float s = 0.f;
-            for (int k = 0; k < rpp; ++k) s += red[k * groups + cg][j];
-            part[(size_t)blockIdx.x * Cp + cg * 8 + j] = s;
-        }
+        for (int j = 0; j < 8; ++j) acc[j] += f[j];
+        *reinterpret_cast<uint4 *>(out + r * Cp + cg * 8) = tm_pack8(f);
     }
+    tm_channel_partials(acc, groups, rpp, cg, r0, Cp, part);
 }
 
 extern "C" long long v2x_channel_sum_workspace_size(long long M, int C) {
-    if (!bn_shape_ok(M, C)) return 0;
+    if (!tm_chan8_shape_ok(M, C)) return 0;
     return (long long)cs_blocks(M, C) * C * (long long)sizeof(float);
 }
 
 extern "C" int v2x_channel_sum_bf16(const uint16_t *x, long long M, int C, float *out, float *workspace, v2x_stream_t stream) {
     V2X_REQUIRE(x && out && workspace, "v2x_channel_sum_bf16: null pointer");
-    V2X_REQUIRE(bn_shape_ok(M, C), "v2x_channel_sum_bf16: needs M > 0 and C in {8, 16, 32, ..., 2048} (C / 8 divides 256), got M=%lld C=%d", M, C);
+    V2X_REQUIRE(tm_chan8_shape_ok(M, C), "v2x_channel_sum_bf16: needs M > 0 and C in {8, 16, 32, ..., 2048} (C / 8 divides 256), got M=%lld C=%d", M, C);
     const int nblk = cs_blocks(M, C);
     hipLaunchKernelGGL(channel_sum_partial_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, M, C, workspace);
-    hipLaunchKernelGGL(channel_sum_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, workspace, nblk, C, out);
+    hipLaunchKernelGGL(channel_sum_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, workspace, nblk, C, (size_t)C, (size_t)1, out);
     V2X_CHECK_LAUNCH("channel_sum kernels");
     return V2X_OK;
 }
@@ -526,11 +468,11 @@ extern "C" long long v2x_cast_pad_chsum_workspace_size(long long M, int Cp) { re
 
 extern "C" int v2x_cast_pad_chsum_f32(const float *x, long long M, int C, int Cp, uint16_t *out, float *sums, float *workspace, v2x_stream_t stream) {
     V2X_REQUIRE(x && out && sums && workspace, "v2x_cast_pad_chsum_f32: null pointer");
-    V2X_REQUIRE(bn_shape_ok(M, Cp) && C > 0 && C % 4 == 0 && C <= Cp, "v2x_cast_pad_chsum_f32: needs M > 0, C %% 4 == 0, C <= Cp, Cp in {8, 16, 32, ...} (Cp / 8 divides 256), got M=%lld C=%d Cp=%d", M, C, Cp);
+    V2X_REQUIRE(tm_chan8_shape_ok(M, Cp) && C > 0 && C % 4 == 0 && C <= Cp, "v2x_cast_pad_chsum_f32: needs M > 0, C %% 4 == 0, C <= Cp, Cp in {8, 16, 32, ...} (Cp / 8 divides 256), got M=%lld C=%d Cp=%d", M, C, Cp);
     V2X_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0, "v2x_cast_pad_chsum_f32: x and out must be 16-byte aligned");
     const int nblk = cs_blocks(M, Cp);
     hipLaunchKernelGGL(cast_pad_chsum_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, M, C, Cp, out, workspace);
-    hipLaunchKernelGGL(channel_sum_finish_kernel, dim3((Cp + 3) / 4), dim3(256), 0, (hipStream_t)stream, workspace, nblk, Cp, sums);
+    hipLaunchKernelGGL(channel_sum_finish_kernel, dim3((Cp + 3) / 4), dim3(256), 0, (hipStream_t)stream, workspace, nblk, Cp, (size_t)Cp, (size_t)1, sums);
     V2X_CHECK_LAUNCH("cast_pad_chsum kernels");
     return V2X_OK;
 }

@@ -5,7 +5,7 @@
 // PyTorch ops it was an expand-copy + a cat forward and two slice copies + a bf16 reduction backward per decoder level (~20 launches, 0.4 ms of a
 // 10-map step).  One launch each way here; the backward's 2x2 sum is four bf16 values added in fp32 in a fixed order (row-major) and rounded
 // once -- what torch's bf16 sum does -- no atomics.
-#include "common.h"
+#include "train_math.h"
 
 namespace {
 struct UpcatArgs {
@@ -34,15 +34,6 @@ __global__ __launch_bounds__(256) void upcat_fwd_kernel(const UpcatArgs a) {
     }
 }
 
-__device__ __forceinline__ void upcat_acc8(float (&s)[8], const uint4 v) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        s[2 * k] += __uint_as_float(w[k] << 16);
-        s[2 * k + 1] += __uint_as_float(w[k] & 0xffff0000u);
-    }
-}
-
 __global__ __launch_bounds__(256) void upcat_bwd_kernel(const UpcatArgs a) {
     const int v0 = a.C0 >> 3, v1 = a.C1 >> 3, vc = v0 + v1;
     const long long n_lo = (long long)a.N * a.H * a.W * v0, n_sk = (long long)a.N * 2 * a.H * 2 * a.W * v1;
@@ -59,11 +50,11 @@ __global__ __launch_bounds__(256) void upcat_bwd_kernel(const UpcatArgs a) {
             const long long row0 = ((n * 2 * a.H + 2 * y) * 2 * a.W + 2 * x) * vc + cv;     // (2y, 2x)
             const long long row1 = row0 + (long long)2 * a.W * vc;                           // (2y + 1, 2x)
             float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            upcat_acc8(s, dc[row0]);
-            upcat_acc8(s, dc[row0 + vc]);
-            upcat_acc8(s, dc[row1]);
-            upcat_acc8(s, dc[row1 + vc]);
-            dlo[i] = make_uint4(pack_bf16x2(s[0], s[1]), pack_bf16x2(s[2], s[3]), pack_bf16x2(s[4], s[5]), pack_bf16x2(s[6], s[7]));
+            tm_acc8(s, dc[row0]);
+            tm_acc8(s, dc[row0 + vc]);
+            tm_acc8(s, dc[row1]);
+            tm_acc8(s, dc[row1 + vc]);
+            dlo[i] = tm_pack8(s);
         } else {
             const long long j = i - n_lo;
             const int cv = (int)(j % v1);

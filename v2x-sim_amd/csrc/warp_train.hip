@@ -6,10 +6,11 @@
 // bit-reproducible).  Here the data gradient is a GATHER: for an affine map the output pixels q whose sample point falls within one pixel
 // of an input pixel p lie in a small parallelogram around M^-1 (p - t) (<= 3 x 3 for a rotation, 2 x 2 for a translation); every thread
 // owns one input pixel, walks those candidates in a fixed order, recomputes each candidate's sample position with the SAME device function
-// as the forward kernel and adds w(q, p) * dout[q] -- the exact transpose of the forward operator, deterministic, no atomics.
+// as the forward kernel and adds w(q, p) * dout[q] -- the exact transpose of the forward operator, deterministic, no atomics.  The geometry
+// (taps, candidate box, recomputed weight) is train_math.h's, shared with v2v_train.hip's two-pass message kernels.
 // A singular or strongly shrinking map (|det M| small: many output pixels per input pixel) widens the candidate box up to the whole map --
 // still exact, only slower.
-#include "common.h"
+#include "train_math.h"
 
 namespace {
 constexpr int WT_CCH = 16;   // channels per thread (the taps / candidates of a pixel are computed once per chunk)
@@ -21,17 +22,6 @@ struct WarpTrainArgs {
     int P, C, H, W;
 };
 
-// sample position (input pixel units) of output pixel (j = column, i = row) under theta: F.affine_grid + the unnormalisation of
-// F.grid_sample with align_corners = False
-__device__ __forceinline__ void warp_sample_pos(const float th[6], int j, int i, int H, int W, float &ix, float &iy) {
-    const float xn = (2.0f * (float)j + 1.0f) / (float)W - 1.0f;
-    const float yn = (2.0f * (float)i + 1.0f) / (float)H - 1.0f;
-    const float gx = th[0] * xn + th[1] * yn + th[2];
-    const float gy = th[3] * xn + th[4] * yn + th[5];
-    ix = ((gx + 1.0f) * (float)W - 1.0f) * 0.5f;
-    iy = ((gy + 1.0f) * (float)H - 1.0f) * 0.5f;
-}
-
 __global__ __launch_bounds__(256) void warp_affine_fwd_kernel(const WarpTrainArgs a) {
     const int p = blockIdx.z, c0 = blockIdx.y * WT_CCH;
     const int pix = blockIdx.x * 256 + threadIdx.x;
@@ -41,26 +31,15 @@ __global__ __launch_bounds__(256) void warp_affine_fwd_kernel(const WarpTrainArg
 #pragma unroll
     for (int k = 0; k < 6; ++k) th[k] = a.theta[p * 6 + k];
     const int i = pix / a.W, j = pix - i * a.W;
-    float ix, iy;
-    warp_sample_pos(th, j, i, a.H, a.W, ix, iy);
-    const float fx = floorf(ix), fy = floorf(iy);
-    // out-of-range sample positions (also inf / nan) contribute nothing: compare in float before converting
-    const bool any = fx >= -1.0f && fx < (float)a.W && fy >= -1.0f && fy < (float)a.H;
-    const int x0 = any ? (int)fx : 0, y0 = any ? (int)fy : 0;
-    const float wx1 = ix - fx, wy1 = iy - fy, wx0 = 1.0f - wx1, wy0 = 1.0f - wy1;
-    const bool vx0 = any && x0 >= 0, vx1 = any && x0 + 1 < a.W, vy0 = any && y0 >= 0, vy1 = any && y0 + 1 < a.H;
-    const float w00 = (vx0 && vy0) ? wx0 * wy0 : 0.f, w01 = (vx1 && vy0) ? wx1 * wy0 : 0.f;
-    const float w10 = (vx0 && vy1) ? wx0 * wy1 : 0.f, w11 = (vx1 && vy1) ? wx1 * wy1 : 0.f;
-    const int o00 = (vx0 && vy0) ? y0 * a.W + x0 : 0, o01 = (vx1 && vy0) ? y0 * a.W + x0 + 1 : 0;
-    const int o10 = (vx0 && vy1) ? (y0 + 1) * a.W + x0 : 0, o11 = (vx1 && vy1) ? (y0 + 1) * a.W + x0 + 1 : 0;
+    const TmWarpTaps t = tm_warp_taps(th, j, i, a.H, a.W);
     const int nc = min(WT_CCH, a.C - c0);
     for (int c = 0; c < nc; ++c) {
         const float *s = a.src + ((size_t)p * a.C + c0 + c) * HW;
         // the same order of additions as at::native's grid_sampler_2d kernel: nw, ne, sw, se
-        float v = s[o00] * w00;
-        v += s[o01] * w01;
-        v += s[o10] * w10;
-        v += s[o11] * w11;
+        float v = s[t.o[0]] * t.w[0];
+        v += s[t.o[1]] * t.w[1];
+        v += s[t.o[2]] * t.w[2];
+        v += s[t.o[3]] * t.w[3];
         a.dst[((size_t)p * a.C + c0 + c) * HW + pix] = v;
     }
 }
@@ -74,38 +53,15 @@ __global__ __launch_bounds__(256) void warp_affine_bwd_kernel(const WarpTrainArg
 #pragma unroll
     for (int k = 0; k < 6; ++k) th[k] = a.theta[p * 6 + k];
     const int y = pix / a.W, x = pix - y * a.W;
-    // sample position as an affine function of the output pixel: (ix, iy) = M (j, i) + t
-    const float fw = (float)a.W, fh = (float)a.H;
-    const float m00 = th[0], m01 = th[1] * fw / fh, m10 = th[3] * fh / fw, m11 = th[4];
-    float t0, t1;
-    warp_sample_pos(th, 0, 0, a.H, a.W, t0, t1);
-    const float det = m00 * m11 - m01 * m10;
-    int jlo = 0, jhi = a.W - 1, ilo = 0, ihi = a.H - 1;
-    if (fabsf(det) > 1e-6f && isfinite(det) && isfinite(t0) && isfinite(t1)) {
-        const float r00 = m11 / det, r01 = -m01 / det, r10 = -m10 / det, r11 = m00 / det;
-        const float qj = r00 * ((float)x - t0) + r01 * ((float)y - t1), qi = r10 * ((float)x - t0) + r11 * ((float)y - t1);
-        // |ix - x| < 1 and |iy - y| < 1  <=>  q in q0 + M^-1 (-1, 1)^2; the slack covers the rounding of the two evaluations
-        const float ej = fabsf(r00) + fabsf(r01) + 1e-2f, ei = fabsf(r10) + fabsf(r11) + 1e-2f;
-        const float a0 = ceilf(qj - ej), a1 = floorf(qj + ej), b0 = ceilf(qi - ei), b1 = floorf(qi + ei);
-        jlo = (int)fmaxf(a0, 0.f);
-        jhi = (int)fminf(a1, fw - 1.f);
-        ilo = (int)fmaxf(b0, 0.f);
-        ihi = (int)fminf(b1, fh - 1.f);
-    }
+    const TmWarpBox b = tm_warp_candidates(th, x, y, a.H, a.W);
     const int nc = min(WT_CCH, a.C - c0);
     float acc[WT_CCH];
 #pragma unroll
     for (int c = 0; c < WT_CCH; ++c) acc[c] = 0.f;
     const float *s = a.src + ((size_t)p * a.C + c0) * HW;
-    for (int i = ilo; i <= ihi; ++i)
-        for (int j = jlo; j <= jhi; ++j) {
-            float ix, iy;
-            warp_sample_pos(th, j, i, a.H, a.W, ix, iy);
-            const float fx = floorf(ix), fy = floorf(iy);
-            // the forward kernel's weights of this output pixel on input pixel (x, y)
-            const float wx = ((float)x == fx) ? 1.0f - (ix - fx) : (((float)x == fx + 1.0f) ? ix - fx : 0.f);
-            const float wy = ((float)y == fy) ? 1.0f - (iy - fy) : (((float)y == fy + 1.0f) ? iy - fy : 0.f);
-            const float w = wx * wy;
+    for (int i = b.ilo; i <= b.ihi; ++i)
+        for (int j = b.jlo; j <= b.jhi; ++j) {
+            const float w = tm_warp_weight(th, j, i, x, y, a.H, a.W);
             if (w == 0.f) continue;
             const int q = i * a.W + j;
 #pragma unroll
