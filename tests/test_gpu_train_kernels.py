@@ -1,7 +1,11 @@
 """Row f-3, first hand-written backward kernels: forward / data gradient / weight gradient of the 3x3 stride-1 convolutions
 on libv2x_amd.so (v2x_conv2d on flipped weights, v2x_conv3x3_wgrad) behind torch.autograd.Function, against
 torch.autograd (MIOpen / CPU fp32) on the SAME bf16-rounded operands.  Tolerances: bf16 storage of y / dx (one rounding of
-the fp32 sums); dW is an fp32 sum of bf16 x bf16 products over N*H*W pixels -> 1e-3 of its scale."""
+the fp32 sums); dW is an fp32 sum of bf16 x bf16 products over N*H*W pixels -> 1e-3 of its scale.
+
+The shapes here are a handful per entry point.  Every channel count the kernels take, both sides of every block cap, the three backward forms of
+the message kernel, edge values and exact-integer sums are swept against float64 in tests/test_gpu_train_sweep.py (references and case tables:
+tests/train_refs.py)."""
 import numpy as np
 import pytest
 import torch

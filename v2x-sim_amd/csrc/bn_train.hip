@@ -7,14 +7,15 @@
 //
 //   forward   (1) bn_partial_kernel<STATS>   per-channel sum x, sum x^2           read x
 //             (2) bn_finish_stats_kernel     mean, biased var -> 1/sqrt(var+eps); running statistics as nn.BatchNorm does
-//             (3) bn_apply_kernel            y = relu(x * a + b) -> bf16          read x, write y     (a = gamma/std, b = beta - mean a)
+//             (3) bn_apply_kernel            y = relu((x - mean) a + beta) -> bf16 read x, write y    (a = gamma / std; the mean is subtracted first, not folded into a shift)
 //   backward  (1) bn_partial_kernel<GRADS>   sum g, sum g xhat,  g = dy * [y > 0] read x, dy          (y recomputed, never stored twice)
 //             (2) bn_finish_grads_kernel     dbeta, dgamma
 //             (3) bn_bwd_apply_kernel        dx = a (g - dbeta/M - xhat dgamma/M) read x, dy, write dx
 //
 // Determinism: a workgroup owns a contiguous run of pixels and writes ONE partial per channel; the finish kernels add the partials
 // in a fixed order in fp64.  No atomics anywhere, so two runs give the same bits (MIOpen's BN backward does not promise that).
-// var = E[x^2] - mean^2 is formed in fp64 from the fp32 partials (a thread adds at most M * C / (8 * 256 * n_blocks) values per channel).
+// var = E[x^2] - mean^2 is formed in fp64 from the fp32 partials (a thread adds at most M * C / (8 * 256 * n_blocks) values per channel in fp32; the
+// workgroup's threads of a channel are added in fp64, and the partial is rounded to fp32 once).
 #include "train_math.h"
 
 constexpr int BN_THREADS = 256;
@@ -92,11 +93,15 @@ __global__ __launch_bounds__(BN_THREADS) void bn_partial_kernel(const BnArgs a) 
         red[t][8 + i] = s1[i];
     }
     __syncthreads();
-    // thread (g, i) for g < G, i < 16 adds the BN_THREADS / G rows of its channel group in row order
+    // thread (g, i) for g < G, i < 16 adds the BN_THREADS / G rows of its channel group in row order -- in fp64: as an fp32 sum this was a serial run of
+    // up to 256 terms (C = 8), 256 / G times the roundings of a thread's own run, which the variance's E[x^2] - mean^2 then amplifies by 1 + mean^2 / var
+    // (invstd up to 18 x torch's fp32 error at C = 8, and enough noise in dbeta / M, dgamma / M to move 1.5e-3 of dx's bf16 roundings at C = 16:
+    // tests/test_gpu_train_sweep.py)
     for (int o = t; o < a.G * 16; o += BN_THREADS) {
         const int gg = o >> 4, i = o & 15;
-        float s = 0.f;
-        for (int r = gg; r < BN_THREADS; r += a.G) s += red[r][i];
+        double sd = 0.0;
+        for (int r = gg; r < BN_THREADS; r += a.G) sd += (double)red[r][i];
+        const float s = (float)sd;
         // [kind][channel][workgroup]: the finish kernel (one workgroup per channel) then reads its channel's partials as contiguous floats -- in the
         // [workgroup][kind][channel] layout of rounds 3-5 every one of its loads touched its own 64-byte line, which 16 workgroups re-read (134 MB of L2
         // traffic per finish launch at 512 channels x 2048 partials)
@@ -178,12 +183,13 @@ __global__ __launch_bounds__(BN_THREADS) void bn_finish_grads_kernel(const BnArg
 __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const BnArgs a) {
     const int t = threadIdx.x;
     const int g = t % a.G;
-    float sc[8], sh[8];
+    float mu[8], sc[8], be[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int c = g * 8 + i;
+        mu[i] = a.mean[c];
         sc[i] = a.gamma[c] * a.invstd[c];
-        sh[i] = fmaf(-a.mean[c], sc[i], a.beta[c]);
+        be[i] = a.beta[c];
     }
     const long long total = a.M * a.G;
     const uint4 *xv = reinterpret_cast<const uint4 *>(a.x);
@@ -193,7 +199,10 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const BnArgs a) {
         tm_unpack8(xv[v], x);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            x[i] = fmaf(x[i], sc[i], sh[i]);
+            // y = (x - mean) * a + beta with a = gamma / std: the mean goes first.  The folded form x * a + b (b = beta - mean a) rounds b at |mean a|,
+            // an absolute error of |mean| / std fp32 ulps of gamma in every y: at mean / std ~ 125 it moved 6e-3 of a map's bf16 roundings
+            // (tests/test_gpu_train_sweep.py, the ill-conditioned case).
+            x[i] = fmaf(x[i] - mu[i], sc[i], be[i]);
             if (a.relu) x[i] = fmaxf(x[i], 0.f);
         }
         yv[v] = tm_pack8(x);

@@ -116,6 +116,15 @@ __device__ __forceinline__ float tm_gru_gates_fwd(float gi_r, float gi_z, float 
 
 // dh -> d gi_r, d gi_z, d gi_n and dpre_n * r (whose channel sums are d bias_hh's n part).  gru_gates_nhwc_kernel<true> repeats these expressions in place:
 // edit the two together.
+// Both copies against float64 on the same bf16 pre-activations (tests/test_gpu_train_sweep.py::test_gru_backward_copies_against_float64, 1x MI355X),
+// at (P, C) = (1001, 32) | (1536, 64):
+//   this function (fp32 out):   mean error 14.4 | 14.2 fp32 ulps of the element, max 2.2e4 | 2.3e5 -- the maximum sits on saturated gates, where 1 - z and 1 - n^2 cancel and
+//                               ANY fp32 evaluation loses the element's low bits: torch's own fp32 ops measure 14.5 | 14.4 mean and the same maxima to the unit; 0.30 | 0.35 of
+//                               the sweep's bar (4 x torch's fp32 error).  Rounded to bf16, 26 of 96 096 | 53 of 294 912 elements differ from the float64 result rounded once.
+//   the NHWC copy (bf16 out):   27 of 96 096 | 56 of 294 912 stored elements differ from the float64 result rounded once (2.8e-4 | 1.9e-4; the sweep allows 1e-3), none by more
+//                               than 0.76 | 0.93 of one bf16 step.
+//   the two copies disagree on 7 | 21 elements after the bf16 store ("about one dgi_n in 10^4"): each is within fp32 rounding of float64, neither is the closer one -- the
+//   disagreement is where an fp32 difference of a few ulps straddles a bf16 rounding boundary.
 __device__ __forceinline__ void tm_gru_gates_bwd(float gi_r, float gi_z, float gi_n, float b_r, float b_z, float b_n, float dh, float &dgi_r, float &dgi_z,
                                                  float &dgi_n, float &dpn_r) {
     const float r = tm_sigmoid(gi_r + b_r), z = tm_sigmoid(gi_z + b_z);
