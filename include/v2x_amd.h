@@ -556,6 +556,35 @@ int v2x_match_detections(const float *det_boxes, const int32_t *det_count, int d
                          const int32_t *gt_count, int gt_cap, int n_img, float iou_thr, int32_t *tp, float *best_iou,
                          v2x_stream_t stream);
 
+/* ---------------------------------------------------------------- f-5: tracking (tools/track: SORT on the detections)
+ * v2x_assign_iou: the association step alone on caller-supplied IoU matrices.  iou fp32 [n][cap_r][cap_c] (rows = detections, columns = tracks),
+ * n_rows / n_cols int32 [n] (clamped to [0, cap_r] / [0, cap_c]), cap_r, cap_c in [1, 64].  direct != 0 (abewley master): when every row and every
+ * column has at most one entry > thr, those entries are the matches; otherwise, and always with direct == 0, the assignment that maximises the summed
+ * IoU over min(rows, cols) pairs (shortest augmenting paths in fp64).  A pair with IoU < thr is unmatched; a NaN or infinite entry reads as 0.
+ * row_to_col int32 [n][cap_r] = the row's column or -1 (rows >= n_rows: -1).  One wave per matrix, every loop bounded by the capacities. */
+int v2x_assign_iou(const float *iou, const int32_t *n_rows, const int32_t *n_cols, int n, int cap_r, int cap_c, float thr, int direct,
+                   int32_t *row_to_col, v2x_stream_t stream);
+/* v2x_sort_step: one frame of SORT (Kalman constant-velocity box filter, IoU association, births and deaths) for n independent streams in ONE
+ * launch, no host round trip (capturable).  Per stream: predict every live track, drop tracks whose predicted box is not finite, associate
+ * (v2x_assign_iou's rule), update the matched tracks (Joseph form), one new track per unmatched detection in detection order, report, remove tracks
+ * with time_since_update > max_age (stable: storage order = ascending id).
+ * det_boxes: box_format 0: fp32 [n][det_cap][4] (x1, y1, x2, y2); 1 / 2: fp32 [n][det_cap][5] (x, y, w, h, yaw) with w (1) / h (2) along the
+ *   heading -- the measurement is the stand-up box of the four corners (what v2x_det_postprocess emits; 2 = Config.box_wh_axis "h_along_heading").
+ * det_count int32 [n]: only the first 64 detections of a map are read (status bit 0 when there were more); < 0 (the post-processor's "more than
+ *   cap candidates" marker): the frame has no detections, status bit 2.
+ * STATE, caller-owned; all-zero = the empty tracker (no init entry):
+ *   trk_f fp32 [n][t_cap][17]: x[7] = (u, v, s, r, u', v', s') -- centre, area, aspect and their rates --, then the covariance's non-zero pattern
+ *         Puu, Puu', Pu'u', Pvv, Pvv', Pv'v', Pss, Pss', Ps's', Prr (with SORT's F, H, Q, R the other entries stay zero);
+ *   trk_i int32 [n][t_cap][5]: id, time_since_update, hits, hit_streak, age;
+ *   stream_i int32 [n][4]: n_tracks, next_id (the number of ids given so far; ids start at 1 and are never reused), frame_count,
+ *         status (sticky bits: 0 detections truncated to 64, 1 births dropped at t_cap, 2 negative det_count).   t_cap in [1, 64].
+ * OUTPUT: the tracks with time_since_update == 0 and (hit_streak >= min_hits or frame_count <= min_hits), in ascending id:
+ *   out_boxes fp32 [n][t_cap][4] (x1, y1, x2, y2 of the updated state), out_ids int32 [n][t_cap], out_det int32 [n][t_cap] (the index of the
+ *   detection the track matched this frame), out_count int32 [n].  Entries >= out_count are not written. */
+int v2x_sort_step(const float *det_boxes, const int32_t *det_count, int n, int det_cap, int box_format, float *trk_f, int32_t *trk_i,
+                  int32_t *stream_i, int t_cap, float iou_thr, int max_age, int min_hits, int direct, float *out_boxes, int32_t *out_ids,
+                  int32_t *out_det, int32_t *out_count, v2x_stream_t stream);
+
 /* ---------------------------------------------------------------- d: calibration probes (measurement)
  * No upstream counterpart.  The roofline fractions bench.py prints are graded against the datasheet peaks (8 TB/s, 2.5 PFLOP/s bf16);
  * these two probes measure, on the box the bench runs on, what a pure streaming kernel and a pure MFMA loop sustain, so that fractions
