@@ -271,6 +271,14 @@ int v2x_conv_tile_rows(int Cout, int epilogue);
 /* Same for the streamed-weights kernel (w_layout 2); 0 = that kernel does not cover (Cout, epilogue). */
 int v2x_conv_stream_tile_rows(int Cout, int epilogue);
 int v2x_conv2d(const v2x_conv_desc *desc, v2x_stream_t stream);
+/* The kernel(s) v2x_conv2d(desc) WOULD launch, from the code path that launches them: the same validation and dispatch run with the launch itself
+ * replaced by a record of the kernel's own symbol name.  buf receives the names as a profiler prints them (template arguments, no argument list:
+ * "conv3x3_stream8g_kernel<96, 2, false>"), a sequence (split-K: partial sums, then the reduce) joined with " + ", NUL-terminated.  Returns what
+ * v2x_conv2d returns for this descriptor (same codes, same v2x_last_error text), V2X_EINVAL if the names do not fit cap bytes.  Nothing is
+ * launched, no tensor pointer is dereferenced and no GPU is needed: without one the dispatch rules that count CUs assume the MI355X's 256 (with
+ * one, the CU count is read as in a launch: hipGetDevice / hipDeviceGetAttribute, the only HIP calls).  The pointers still count: they must be
+ * non-null, and the 1x1 streaming kernel is chosen only for 16-byte aligned in0 / out / weight / scale / shift, as in a launch. */
+int v2x_conv2d_plan(const v2x_conv_desc *desc, char *buf, size_t cap);
 /* second(first(x)) for two consecutive HBM-bound layers with the intermediate map kept on chip (conv_halo_pair.hip):
  * replaces Backbone.py::LidarEncoder's conv_pre_1 + bn + relu + conv_pre_2 + bn + relu.  Both descriptors: 3x3, stride 1,
  * pad 1, w_layout 1, C0 = 32 (13 real + zero-weight padding for the first), C1 = 0, Cout = 32, bf16 epilogue;

@@ -91,7 +91,7 @@ def test_parity_class_kernel_against_the_same_bf16_operands(device, N, H, W):
     x_up, x_sk = _inputs(N, 64, 32, H, W, seed=H + W)
     scale, shift = packing.fold_bn(conv.bias, bn, 32)
     pc = packing.pack_conv_halo_parity("conv8_1", conv.weight, scale, shift, C0=64, C1=32, device=device)
-    assert ops.conv_kernel_name(pc, H, W) == "conv3x3_halo_ppc_kernel<64, 32, 32>"
+    assert ops.conv_kernel_name(pc, H, W, False, N) == "conv3x3_halo_ppc_kernel<64, 32, 32>"
     got = from_nhwc(_run(ops, pc, x_up, x_sk, device))
     ref = _same_operands_ref(packing, conv, bn, x_up, x_sk, 64)
     assert got.shape == ref.shape
@@ -212,7 +212,7 @@ def test_streamed_parity_class_kernel_against_the_same_bf16_operands(device, C0,
     x_up, x_sk = _inputs(N, C0, C1, H, W, seed=H + W + N)
     scale, shift = packing.fold_bn(conv.bias, bn, Cout)
     pc = packing.pack_conv_stream_parity("conv5_1", conv.weight, scale, shift, C0=C0, C1=C1, device=device)
-    assert ops.conv_kernel_name(pc, H, W) == ("conv3x3_stream8q_kernel" if Cout == 64 else "conv3x3_stream8p_kernel") and pc.w_kpad == 16 * C0 + 9 * C1
+    assert ops.conv_kernel_name(pc, H, W, False, N) == ("conv3x3_stream8q_kernel" if Cout == 64 else "conv3x3_stream8p_kernel") and pc.w_kpad == 16 * C0 + 9 * C1
     xu, xs = to_nhwc_bf16(x_up, device), to_nhwc_bf16(x_sk, device)
     y = ops.conv2d(pc, xu, xs)
     again = [ops.conv2d(pc, xu, xs) for _ in range(2)]

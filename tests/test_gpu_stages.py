@@ -592,7 +592,9 @@ def test_halo_pingpong_equals_4wave_kernel_bitwise(device, cup, c, cout, N, H, W
     tune("HALO_PP", 1)
     new = [run().clone() for _ in range(3)]
     tune.reset("HALO_PP")
-    assert ops.conv_kernel_name(pc, H, W) == "conv3x3_halo_pp_kernel<%d, %d, %d, 0>" % (cup, c, cout)
+    # (the ping-pong kernel pairs tiles: an odd tile count -- 3 maps of 40 x 96 -- takes the 4-wave kernel whatever the switch says)
+    paired = (N * (H // 8) * (W // 32)) % 2 == 0
+    assert ops.conv_kernel_name(pc, H, W, False, N) == ("conv3x3_halo_pp_kernel<%d, %d, %d, 0>" if paired else "conv3x3_halo_kernel<%d, %d, %d, 0, 0>") % (cup, c, cout)
     assert all(torch.equal(old.view(torch.int16), y.view(torch.int16)) for y in new)
     if N <= 3:
         ref = _halo_ref(x, w, scale, shift, True, x_up)
@@ -615,7 +617,7 @@ def test_halo_pingpong_chained_1x1(device, N, H, W):
     pp = packing.pack_conv_halo("c", w1, s1, t1, relu=True, chain=(w2, s2, t2, True), device=device)
     st = packing.pack_conv_stream("c", w1, s1, t1, relu=True, chain=(w2, s2, t2, True), device=device)
     xs = to_nhwc_bf16(x, device)
-    assert ops.conv_kernel_name(pp, H, W) == "conv3x3_halo_pp_kernel<0, 64, 64, 64>"
+    assert ops.conv_kernel_name(pp, H, W, False, N) == "conv3x3_halo_pp_kernel<0, 64, 64, 64>"
     a = ops.conv2d(pp, xs)
     assert all(torch.equal(a, ops.conv2d(pp, xs)) for _ in range(3))
     b = ops.conv2d(st, xs)
@@ -645,7 +647,9 @@ def test_halo_chain_odd_tile_count(device, H, W):
     xs = to_nhwc_bf16(x, device)
     assert ((H // 8) * (W // 32)) % 2 == 1
     even = ops.conv2d(pp, xs)                          # 4 maps: even tile count -> ping-pong kernel
+    assert ops.conv_kernel_name(pp, H, W, False, 4) == "conv3x3_halo_pp_kernel<0, 64, 64, 64>"
     for n in (1, 3):
+        assert ops.conv_kernel_name(pp, H, W, False, n) == "conv3x3_halo_kernel<0, 64, 64, 64, 1>"
         odd = ops.conv2d(pp, xs[:n].contiguous())      # odd tile count -> 4-wave kernel
         assert torch.equal(odd, even[:n]), n
     hid = bf16r(_halo_ref(x, w1, s1, t1, True))

@@ -162,6 +162,8 @@ def test_stream_chain_conv1x1(device, hw, ch, tune):
     assert torch.allclose(got, ref, atol=3e-2, rtol=2 ** -6), float((got - ref).abs().max())
     assert float((got - ref).abs().mean()) < 2e-3
     if ch == 128 and H % 16 == 0 and W % 32 == 0:   # 8-wave and 4-wave kernels: same K order, same epilogue -> same bits
+        # (two maps are below the few_chain_tiles bound of the dispatch: the launch above already was the 4-wave kernel's)
+        assert ops.conv_kernel_name(pc, H, W, False, 2) == "conv3x3_stream_kernel<128, 8, 32, 1, false>"
         tune("STREAM_WAVES", 4)
         y4 = back(ops.conv2d(pc, nhwc(x, device)))
         assert torch.equal(got, y4)
@@ -210,7 +212,7 @@ def test_stream8_equals_stream4_bitwise(device, cfg, tune):
     # products summed in another order -> at most one bf16 rounding apart, and bit-stable over launches
     tune.reset("STREAM_G")
     yg = run()
-    assert ops.conv_kernel_name(pc, H, W).startswith("conv3x3_stream8g_kernel")
+    assert ops.conv_kernel_name(pc, H, W, False, N).startswith("conv3x3_stream8g_kernel<")
     d = (yg.float() - y8.float()).abs()
     assert torch.allclose(yg.float(), y8.float(), atol=2e-3 if not gru else 2 ** -7, rtol=2 ** -7), float(d.max())
     assert float((yg != y8).float().mean()) < 0.02
@@ -219,10 +221,10 @@ def test_stream8_equals_stream4_bitwise(device, cfg, tune):
     # the two wave tilings of stream8g (all channels x 64 pixels per wave / half the channels x 128 pixels) walk K in the same order:
     # bit-identical, for the plain layers (default: new tiling) and the ConvGRU (default: old tiling)
     tune("STREAM_WT", 0)
-    assert ops.conv_kernel_name(pc, H, W).endswith(", false>")
+    assert ops.conv_kernel_name(pc, H, W, False, N) == "conv3x3_stream8g_kernel<%d, %d, false>" % ((96, 2) if gru else (128, 0))
     y_old = run()
     tune("STREAM_WT", 2)
-    assert ops.conv_kernel_name(pc, H, W).endswith(", true>")
+    assert ops.conv_kernel_name(pc, H, W, False, N) == "conv3x3_stream8g_kernel<%d, %d, true>" % ((96, 2) if gru else (128, 0))
     y_new = run()
     tune.reset("STREAM_WT")
     assert torch.equal(y_old, yg) and torch.equal(y_new, yg)
@@ -328,12 +330,12 @@ def test_stride2_three_tap_kernel_vs_torch_and_one_tap(device, cfg, tune):
     pc = packing.pack_conv_stream("s2", w, scale, shift, C0=C, stride=2, device=device)
     xd = nhwc(x, device)
     tune("S2_G", 2)
-    assert ops.conv_kernel_name(pc, H, W, False, N).startswith("conv3x3_s2g_kernel")
+    assert ops.conv_kernel_name(pc, H, W, False, N) == "conv3x3_s2g_kernel<%s>" % ("8, 32" if (W // 2) % 32 == 0 else "16, 16")
     got = ops.conv2d(pc, xd)
     for _ in range(3):
         assert torch.equal(ops.conv2d(pc, xd), got)
     tune("S2_G", 0)
-    assert ops.conv_kernel_name(pc, H, W, False, N).startswith("conv3x3_s2_stream_kernel")
+    assert ops.conv_kernel_name(pc, H, W, False, N) == "conv3x3_s2_stream_kernel<128, %s, false>" % ("4, 32" if W % 64 == 0 else "8, 16")
     one = ops.conv2d(pc, xd)
     got, one = back(got), back(one)
     assert got.shape == ref.shape == (N, Cout, H // 2, W // 2)
@@ -374,7 +376,7 @@ def test_wide_kernel_equals_256_pixel_kernel_bitwise(device, cfg, tune):
     # default for the plain epilogue: three taps per synchronisation (conv3x3_wide3_kernel), K order (chunk, kx, ky): the same products
     # summed in another order -> at most one bf16 rounding apart, and bit-stable over launches
     y3 = run()
-    name = ops.conv_kernel_name(pc, H, W)
+    name = ops.conv_kernel_name(pc, H, W, False, N)
     three = not chain and cup + c >= 96
     assert name == ("conv3x3_wide3_kernel<64>" if three else "conv3x3_wide_kernel<64, %d>" % (1 if chain else 0)), name
     if not three:
@@ -537,3 +539,38 @@ def test_stride2_split_k_form_vs_torch_and_unsplit(device, cfg, tune):
     assert sk == 0 or (2 <= sk <= chunks // 2)
     if C == 256 and Cout == 512:
         assert sk == 4                                  # conv4_1 at one frame: 40 tiles, 8 chunks
+
+
+def test_plan_call_leaves_the_lds_opt_in_to_the_first_launch():
+    """ops.conv_kernel_name asks the library which kernel a layer takes (v2x_conv2d_plan: the dispatch with the launch helper recording instead of launching).
+    Such a call must not use up the helper's once-per-device state: in a FRESH process (a child; nothing has launched the kernel there) the name of a
+    32 -> 128 layer on one 16 x 32 map -- stream8g, 153 KiB of LDS, impossible without the opt-in -- is asked first, then the layer is launched and compared
+    with torch fp32 on the same bf16 operands at test_stream_conv_vs_torch's tolerance.  A consumed flag shows as a launch error."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = """
+import sys
+sys.path[:0] = [%r, %r]
+import torch
+import torch.nn.functional as F
+from v2x_sim_amd import ops, packing
+dev = torch.device("cuda:0")
+g = torch.Generator().manual_seed(32 + 128)
+r = lambda t: t.to(torch.bfloat16).to(torch.float32)
+x = r(torch.randn(1, 32, 16, 32, generator=g))
+w = torch.randn(128, 32, 3, 3, generator=g) * (2.0 / (32 * 9)) ** 0.5
+scale, shift = torch.rand(128, generator=g) + 0.5, torch.randn(128, generator=g) * 0.2
+ref = F.relu(F.conv2d(x, r(w), None, 1, 1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
+pc = packing.pack_conv_stream("t", w, scale, shift, C0=32, device=dev)
+print("NAME", ops.conv_kernel_name(pc, 16, 32))
+y = ops.conv2d(pc, x.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).to(dev))
+got = y.float().cpu().permute(0, 3, 1, 2)
+print("MAXERR", float((got - ref).abs().max()))
+print("CLOSE", bool(torch.allclose(got, ref, atol=2e-3, rtol=2 ** -7)))
+""" % (root, os.path.join(root, "v2x-sim_amd"))
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    print(p.stdout)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert "NAME conv3x3_stream8g_kernel<128, 0, true>\n" in p.stdout and "CLOSE True" in p.stdout, p.stdout + p.stderr

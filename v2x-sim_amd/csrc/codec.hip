@@ -194,14 +194,13 @@ static int codec_launch(const CodecArgs &a, hipStream_t s) {
     constexpr int KS1 = C / 32, CT1 = CC >= 16 ? CC / 16 : 1, KS2 = CC >= 32 ? CC / 32 : 1, CT2 = C / 16;
     constexpr int F = (MODE != CODEC_DECOMPRESS ? CT1 * KS1 : 0) + (MODE != CODEC_COMPRESS ? CT2 * KS2 : 0);
     constexpr int NT = LDSW ? 512 : 256;
-    const size_t lds = LDSW ? (size_t)F * 1024 : 0;
-    auto kern = codec_kernel<C, CC, MODE, LDSW>;
-    if (lds >= 64 * 1024) {
+    constexpr int lds = LDSW ? F * 1024 : 0;
+    if (lds >= 64 * 1024) {   // (kept beside the helper, which asks for none here: this site reports a refused opt-in by itself)
         static v2x_once_per_device once;
         if (v2x_first_use_on_device(once)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(codec_kernel<C, CC, MODE, LDSW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             if (e != hipSuccess) {
-                v2x_set_error("v2x_codec: hipFuncSetAttribute(%zu bytes of LDS): %s", lds, hipGetErrorString(e));
+                v2x_set_error("v2x_codec: hipFuncSetAttribute(%zu bytes of LDS): %s", (size_t)lds, hipGetErrorString(e));
                 return V2X_EIO;
             }
         }
@@ -211,9 +210,7 @@ static int codec_launch(const CodecArgs &a, hipStream_t s) {
     // LDS form: one 8-wave workgroup per CU while the weights are > 80 KiB, two below; register form: the register file holds 2 workgroups per CU
     const int cap = v2x_num_cus() * (LDSW ? (lds > 80 * 1024 ? 1 : 2) : 2);
     if (grid > cap) grid = cap;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, s, a);
-    V2X_CHECK_LAUNCH("codec_kernel");
-    return V2X_OK;
+    return v2x_launch<codec_kernel<C, CC, MODE, LDSW>, 0>("codec_kernel", dim3(grid), dim3(NT), lds, s, a);
 }
 
 template <int C, int CC, int MODE>

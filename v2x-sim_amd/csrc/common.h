@@ -68,6 +68,30 @@ static inline bool v2x_first_use_on_device(v2x_once_per_device &o) {
     return true;
 }
 
+// THE kernel launch of the library: the > 64 KiB dynamic-LDS opt-in once per device and kernel (the state is per instantiation, i.e. per kernel), the
+// launch, the error check.  LDS_OPT_IN: the bytes the opt-in asks for -- by default the launch's own lds_bytes (a constant of the kernel at those
+// sites), a kernel whose launches differ in size names its maximum, 0 = no opt-in.  `what`: the kernel as the error text names it.
+// Plan mode (v2x_conv2d_plan, api.hip): while the calling thread's v2x_plan_sink is set, NOTHING is launched and this helper makes no HIP call -- the
+// kernel that would have been launched is recorded by its own symbol name and the once-per-device state stays untouched (a later real launch
+// still makes its opt-in).  (The dispatch around it still asks v2x_num_cus(): hipGetDevice / hipDeviceGetAttribute, 256 without a device.)
+// __thread, not thread_local: a plain pointer without dynamic initialisation, so a launch reads it without the C++ TLS wrapper call.
+struct v2x_launch_plan;
+extern __thread v2x_launch_plan *v2x_plan_sink;
+int v2x_plan_record(const void *kernel, const char *what);
+template <auto Kern, int LDS_OPT_IN = -1, typename... A>
+static inline int v2x_launch(const char *what, dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const A &... args) {
+    if (v2x_plan_sink) return v2x_plan_record(reinterpret_cast<const void *>(Kern), what);
+    const int opt_in = LDS_OPT_IN >= 0 ? LDS_OPT_IN : lds_bytes;
+    if (opt_in > 0) {
+        static v2x_once_per_device attr_once;
+        if (v2x_first_use_on_device(attr_once))
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, opt_in);
+    }
+    hipLaunchKernelGGL(Kern, grid, block, lds_bytes, s, args...);
+    V2X_CHECK_LAUNCH(what);
+    return V2X_OK;
+}
+
 // fp32 -> bf16, round-to-nearest-even (matches torch .to(torch.bfloat16) for finite values)
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
     uint32_t u = __float_as_uint(f);

@@ -120,9 +120,7 @@ static int launch_c1(const C1Args &a, hipStream_t s) {
     int grid = (n_frag + 4 * PF - 1) / (4 * PF);                 // one run of PF fragments per wave ...
     const int cap = v2x_num_cus() * 8;                           // ... up to 8 workgroups (32 waves) per CU, then the waves loop
     if (grid > cap) grid = cap;
-    hipLaunchKernelGGL((conv1x1_stream_kernel<KS, CT, F32, PF>), dim3(grid), dim3(256), 0, s, a);
-    V2X_CHECK_LAUNCH("conv1x1_stream_kernel");
-    return V2X_OK;
+    return v2x_launch<conv1x1_stream_kernel<KS, CT, F32, PF>>("conv1x1_stream_kernel", dim3(grid), dim3(256), 0, s, a);
 }
 
 template <int KS, bool F32>

@@ -1073,16 +1073,9 @@ static int launch_halo_pp(const HaloArgs &a, hipStream_t s) {
     constexpr int NS0 = C0 ? round64(PH0 * PW0 * (C0 / 8)) : 0;
     constexpr int smem = 9 * (C0 + C1) / 8 * COUT * 16 + 2 * (NS0 + NS1) * 16 + 2 * COUT * 4 + 2 * COUT2 * 4;
     static_assert(smem <= 160 * 1024, "LDS budget");
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_halo_pp_kernel<C0, C1, COUT, COUT2>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
     int grid = 256;                       // one 8-wave workgroup per CU, persistent over tile pairs
     if (grid > a.n_tiles / 2) grid = a.n_tiles / 2;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_halo_pp_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_halo_pp_kernel<C0, C1, COUT, COUT2>>("conv3x3_halo_pp_kernel", dim3(grid), dim3(512), smem, s, a);
 }
 
 // ---- parity-class ("sub-pixel") form of the decoder's upsample -> concat -> 3x3 layers (conv8_1) ---------------------------------
@@ -1327,16 +1320,9 @@ static int launch_halo_ppc(const HaloArgs &a, hipStream_t s) {
     constexpr int NS0 = round64(PH0 * PW0 * (C0 / 8));
     constexpr int smem = (16 * C0 + 9 * C1) / 8 * COUT * 16 + 2 * (NS0 + NS1) * 16 + 2 * COUT * 4;
     static_assert(smem <= 160 * 1024, "LDS budget");
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_halo_ppc_kernel<C0, C1, COUT>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
     int grid = 256;                       // one 8-wave workgroup per CU, persistent over tile pairs
     if (grid > (a.n_tiles + 1) / 2) grid = (a.n_tiles + 1) / 2;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_halo_ppc_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_halo_ppc_kernel<C0, C1, COUT>>("conv3x3_halo_ppc_kernel", dim3(grid), dim3(512), smem, s, a);
 }
 
 // ---- host side ---------------------------------------------------------------------------------
@@ -1349,19 +1335,12 @@ static int launch_halo_sb(const HaloArgs &a, hipStream_t s) {
     // SLOWER with a 4th workgroup (628 / 577 / 649 us) and keep the padded 40-KiB allocation = 3 per CU.
     constexpr int smem = 9 * C1 / 8 * COUT * 16 + (BITS ? PH * PW * (C1 / 8) : round64(PH * PW * (C1 / 8))) * 16 +
                          (COUT2 == 0 ? 2 * COUT * 4 : 0);   // + scale/shift
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_halo_sb_kernel<C0, C1, COUT, COUT2, EPI2, BITS>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
     int per_cu = (160 * 1024 - 2048) / smem;  // leave a little LDS slack: exactly-full allocations may not co-reside
     if (per_cu > 4) per_cu = 4;
     if (per_cu < 1) per_cu = 1;
     int grid = 256 * per_cu;
     if (grid > a.n_tiles) grid = a.n_tiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_halo_sb_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_halo_sb_kernel<C0, C1, COUT, COUT2, EPI2, BITS>>("conv3x3_halo_sb_kernel", dim3(grid), dim3(256), smem, s, a);
 }
 
 template <int C0, int C1, int COUT, int COUT2, int EPI2>
@@ -1370,17 +1349,10 @@ static int launch_halo(const HaloArgs &a, hipStream_t s) {
     constexpr int NS0 = C0 ? round64(PH0 * PW0 * (C0 / 8)) : 0;
     constexpr int smem = 9 * (C0 + C1) / 8 * COUT * 16 + 2 * (NS0 + NS1) * 16 + (COUT2 == 0 ? 2 * COUT * 4 : 0);
     static_assert(smem <= 160 * 1024, "LDS budget");
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_halo_kernel<C0, C1, COUT, COUT2, EPI2>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
     const int per_cu = (160 * 1024) / smem >= 2 ? 2 : 1;
     int grid = 256 * per_cu;
     if (grid > a.n_tiles) grid = a.n_tiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_halo_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_halo_kernel<C0, C1, COUT, COUT2, EPI2>>("conv3x3_halo_kernel", dim3(grid), dim3(256), smem, s, a);
 }
 
 // Returns V2X_OK if handled, 1 if the shape is not one the halo kernel covers (caller falls back

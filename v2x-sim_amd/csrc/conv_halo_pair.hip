@@ -384,15 +384,8 @@ extern "C" int v2x_conv2d_pair(const v2x_conv_desc *first, const v2x_conv_desc *
     a.tiles_x = a.W / pair::TW;
     a.tiles_y = a.H / pair::TH;
     a.n_tiles = a.N * a.tiles_x * a.tiles_y;
-    static v2x_once_per_device attr_once;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_pair_bits_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, pair::SMEM);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_pair_bits_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, pair::SMEM);
-    }
     int grid = v2x_num_cus() * 2;
     if (grid > a.n_tiles) grid = a.n_tiles;
-    if (a.x4) hipLaunchKernelGGL(conv3x3_pair_bits_kernel<true>, dim3(grid), dim3(256), pair::SMEM, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(conv3x3_pair_bits_kernel<false>, dim3(grid), dim3(256), pair::SMEM, (hipStream_t)stream, a);
-    V2X_CHECK_LAUNCH("conv3x3_pair_bits_kernel");
-    return V2X_OK;
+    if (a.x4) return v2x_launch<conv3x3_pair_bits_kernel<true>>("conv3x3_pair_bits_kernel", dim3(grid), dim3(256), pair::SMEM, (hipStream_t)stream, a);
+    return v2x_launch<conv3x3_pair_bits_kernel<false>>("conv3x3_pair_bits_kernel", dim3(grid), dim3(256), pair::SMEM, (hipStream_t)stream, a);
 }

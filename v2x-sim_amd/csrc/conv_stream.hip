@@ -1219,28 +1219,16 @@ template <int BCO, int EPI, bool WT = false>
 static int launch_stream8g(const StreamArgs &a, hipStream_t s) {
     constexpr int smem = 3 * 3 * BCO * 64 + 2 * PATCH8_BYTES + 1024;   // 153 KiB at 128 rows, 135 KiB at 96 (+1 KiB: epilogue parameters)
     static_assert(smem <= 160 * 1024, "LDS budget");
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_stream8g_kernel<BCO, EPI, WT>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
     const int n_tiles = a.n_px_tiles * a.n_co_tiles;
     int grid = n_tiles;
     int g = v2x_num_cus() / a.n_co_tiles * a.n_co_tiles;   // persistent: a workgroup's tiles share one channel tile
     if (g > 0 && g < n_tiles) grid = g;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_stream8g_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_stream8g_kernel<BCO, EPI, WT>>("conv3x3_stream8g_kernel", dim3(grid), dim3(512), smem, s, a);
 }
 
 template <int BCO, int EPI>
 static int launch_stream8(const StreamArgs &a, hipStream_t s) {
     constexpr int smem = RING * BCO * 64 + 2 * PATCH8_BYTES + (EPI == SEPI_CHAIN ? chain_lds_bytes<BCO>() : 0);  // 112 KiB at BCO=128 (+33 chained): one 8-wave workgroup per CU
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_stream8_kernel<BCO, EPI>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
     // persistent grid: one workgroup per CU, rounded down to a multiple of n_co_tiles so that a workgroup's tiles
     // (bid, bid + grid, ...) all belong to one channel tile; fewer tiles than CUs (or a channel-tile count that does not
     // divide) -> one tile per workgroup.  V2X_STREAM_PERSIST=0 forces the one-tile form (A/B runs).
@@ -1250,9 +1238,7 @@ static int launch_stream8(const StreamArgs &a, hipStream_t s) {
         int g = v2x_num_cus() / a.n_co_tiles * a.n_co_tiles;
         if (EPI != SEPI_CHAIN && g > 0 && g < n_tiles && ((a.C0 + a.C1) >> 5) >= 2) grid = g;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_stream8_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_stream8_kernel<BCO, EPI>>("conv3x3_stream8_kernel", dim3(grid), dim3(512), smem, s, a);
 }
 
 // ---- "wide" 4-wave form for the 64-row layers ----------------------------------------------------------
@@ -1614,65 +1600,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 template <int BCO>
 static int launch_wide3(const StreamArgs &a, hipStream_t s) {
     constexpr int smem = 3 * 3 * BCO * 64 + WPATCH_BYTES;   // 75 KiB: two workgroups per CU
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_wide3_kernel<BCO>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
-    hipLaunchKernelGGL(kern, dim3(a.n_px_tiles * a.n_co_tiles), dim3(256), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_wide3_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_wide3_kernel<BCO>>("conv3x3_wide3_kernel", dim3(a.n_px_tiles * a.n_co_tiles), dim3(256), smem, s, a);
 }
 
 template <int BCO, int EPI>
 static int launch_wide(const StreamArgs &a, hipStream_t s) {
     constexpr int smem = RING * BCO * 64 + WPATCH_BYTES + (EPI == SEPI_CHAIN ? chain_lds_bytes<BCO>() : 0);   // 55 KiB (+8.5 chained): two workgroups per CU
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_wide_kernel<BCO, EPI>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
-    hipLaunchKernelGGL(kern, dim3(a.n_px_tiles * a.n_co_tiles), dim3(256), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_wide_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_wide_kernel<BCO, EPI>>("conv3x3_wide_kernel", dim3(a.n_px_tiles * a.n_co_tiles), dim3(256), smem, s, a);
 }
 
 // ---- host side -----------------------------------------------------------------------------------
 template <int BCO, int TH, int TW, int EPI>
 static int launch_stream(const StreamArgs &a, hipStream_t s) {
     constexpr int smem = RING * BCO * 64 + 2 * PATCH_BYTES;  // 80 KiB at BCO=128: two workgroups per CU
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_stream_kernel<BCO, TH, TW, EPI>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
-    hipLaunchKernelGGL(kern, dim3(a.n_px_tiles * a.n_co_tiles), dim3(256), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_stream_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_stream_kernel<BCO, TH, TW, EPI>>("conv3x3_stream_kernel", dim3(a.n_px_tiles * a.n_co_tiles), dim3(256), smem, s, a);
 }
 
 // split-K pair of launches (small batches: a.ksplit chunk ranges per tile so that few tiles still fill the chip)
 template <int BCO, int TH, int TW, int EPI>
 static int launch_stream_splitk(const StreamArgs &a, hipStream_t s) {
     constexpr int smem = RING * BCO * 64 + 2 * PATCH_BYTES;
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_stream_kernel<BCO, TH, TW, SEPI_BF16, true>;   // (the epilogue is the reduce kernel's)
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
-    hipLaunchKernelGGL(kern, dim3(a.n_px_tiles * a.n_co_tiles, a.ksplit), dim3(256), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_stream_kernel(split-K)");
+    // (SEPI_BF16: the epilogue is the reduce kernel's)
+    const int rc = v2x_launch<conv3x3_stream_kernel<BCO, TH, TW, SEPI_BF16, true>>("conv3x3_stream_kernel(split-K)", dim3(a.n_px_tiles * a.n_co_tiles, a.ksplit),
+                                                                                   dim3(256), smem, s, a);
+    if (rc != V2X_OK) return rc;
     const long long npix = (long long)a.N * a.H * a.W;
     const long long threads = npix * (a.Cout / 4);
-    int grid = (int)((threads + 255) / 256 < 4096 ? (threads + 255) / 256 : 4096);
-    if (EPI == SEPI_GRU)
-        hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3(grid), dim3(256), 0, s, a.ws, a.ksplit, npix, a.w_rows, a.Cout, a.scale, a.shift, a.relu,
-                           reinterpret_cast<uint16_t *>(a.out), a.out_cstride, a.out_coff);
-    else
-        hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(grid), dim3(256), 0, s, a.ws, a.ksplit, npix, a.w_rows, a.Cout, a.scale, a.shift, a.relu,
-                           reinterpret_cast<uint16_t *>(a.out), a.out_cstride, a.out_coff);
-    V2X_CHECK_LAUNCH("splitk_reduce_kernel");
-    return V2X_OK;
+    const int grid = (int)((threads + 255) / 256 < 4096 ? (threads + 255) / 256 : 4096);
+    return v2x_launch<splitk_reduce_kernel<EPI == SEPI_GRU>>("splitk_reduce_kernel", dim3(grid), dim3(256), 0, s, a.ws, a.ksplit, npix, a.w_rows, a.Cout, a.scale, a.shift,
+                                                            a.relu, reinterpret_cast<uint16_t *>(a.out), a.out_cstride, a.out_coff);
 }
 
 // the plain-epilogue reduce of a split-K launch, for the stride-2 kernel's split form (conv_stream_s2.hip)
@@ -1680,9 +1636,8 @@ int v2x_launch_splitk_reduce(const float *ws, int ksplit, long long npix, int w_
                              uint16_t *out, int out_cstride, int out_coff, hipStream_t s) {
     const long long threads = npix * (Cout / 4);
     const int grid = (int)((threads + 255) / 256 < 4096 ? (threads + 255) / 256 : 4096);
-    hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(grid), dim3(256), 0, s, ws, ksplit, npix, w_rows, Cout, scale, shift, relu, out, out_cstride, out_coff);
-    V2X_CHECK_LAUNCH("splitk_reduce_kernel");
-    return V2X_OK;
+    return v2x_launch<splitk_reduce_kernel<false>>("splitk_reduce_kernel", dim3(grid), dim3(256), 0, s, ws, ksplit, npix, w_rows, Cout, scale, shift, relu, out, out_cstride,
+                                                   out_coff);
 }
 
 // rows per channel tile the stream kernel uses for (Cout, epilogue); 0 = unsupported

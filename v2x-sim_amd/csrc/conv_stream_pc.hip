@@ -662,24 +662,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 int v2x_conv_stream_pc_launch(const StreamArgs &a, hipStream_t s) {
-    static v2x_once_per_device attr_once;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_stream8p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, pcs::SMEM);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_stream8q_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, pcq::SMEM);
-    }
     if (a.Cout == 64) {   // 16 x 64 regions (the dispatcher set tiles_x = W / 64), one channel tile
         int grid = a.n_px_tiles;
         const int g = v2x_num_cus();
         if (g > 0 && g < grid) grid = g;
-        hipLaunchKernelGGL(conv3x3_stream8q_kernel, dim3(grid), dim3(512), pcq::SMEM, s, a);
-        V2X_CHECK_LAUNCH("conv3x3_stream8q_kernel");
-        return V2X_OK;
+        return v2x_launch<conv3x3_stream8q_kernel>("conv3x3_stream8q_kernel", dim3(grid), dim3(512), pcq::SMEM, s, a);
     }
     const int n_tiles = a.n_px_tiles * a.n_co_tiles;
     int grid = n_tiles;
     const int g = v2x_num_cus() / a.n_co_tiles * a.n_co_tiles;   // persistent: a workgroup's tiles share one channel tile
     if (g > 0 && g < n_tiles) grid = g;
-    hipLaunchKernelGGL(conv3x3_stream8p_kernel, dim3(grid), dim3(512), pcs::SMEM, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_stream8p_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_stream8p_kernel>("conv3x3_stream8p_kernel", dim3(grid), dim3(512), pcs::SMEM, s, a);
 }

@@ -844,32 +844,18 @@ static int launch_s2g(const S2Args &a, hipStream_t s) {
     using G = S2GGeom<TH, TW>;
     constexpr int smem = 3 * 3 * 128 * 64 + (G::E_PIECES + G::O_PIECES) * 1024 + 2 * 128 * 4 + ((V2X_S2G_DBG_BUILD & 64) ? 2 * 96 * 8 * 4 : 0);   // 72 + 70 + 1 KiB
     static_assert(smem <= 160 * 1024, "LDS budget");
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_s2g_kernel<TH, TW>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
     const int n_tiles = a.n_px_tiles * a.n_co_tiles;
     int grid = n_tiles;
     const int g = v2x_num_cus() / a.n_co_tiles * a.n_co_tiles;   // persistent: a workgroup's tiles share one channel tile
     if (g > 0 && g < n_tiles) grid = g;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_s2g_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_s2g_kernel<TH, TW>>("conv3x3_s2g_kernel", dim3(grid), dim3(512), smem, s, a);
 }
 
 static int launch_s2_resident(const S2Args &a, hipStream_t s) {
     constexpr int smem = 9 * 64 * 64 + S2_PATCH_BYTES + 512;   // 36 + 37 KiB + scale/shift
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_s2_resident_kernel<64>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
     int grid = 512;                                       // two workgroups per CU
     if (grid > a.n_px_tiles) grid = a.n_px_tiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_s2_resident_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_s2_resident_kernel<64>>("conv3x3_s2_resident_kernel", dim3(grid), dim3(256), smem, s, a);
 }
 
 int v2x_launch_splitk_reduce(const float *ws, int ksplit, long long npix, int w_rows, int Cout, const float *scale, const float *shift, int relu,
@@ -878,13 +864,9 @@ int v2x_launch_splitk_reduce(const float *ws, int ksplit, long long npix, int w_
 template <int BCO, int TH, int TW>
 static int launch_s2_splitk(const S2Args &a, hipStream_t s) {
     constexpr int smem = S2_RING * BCO * 64 + S2_PATCH_BYTES + 2 * BCO * 4;
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_s2_stream_kernel<BCO, TH, TW, true>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
-    hipLaunchKernelGGL(kern, dim3(a.n_px_tiles * a.n_co_tiles, a.ksplit), dim3(256), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_s2_stream_kernel (split-K)");
+    const int rc = v2x_launch<conv3x3_s2_stream_kernel<BCO, TH, TW, true>>("conv3x3_s2_stream_kernel (split-K)", dim3(a.n_px_tiles * a.n_co_tiles, a.ksplit), dim3(256),
+                                                                           smem, s, a);
+    if (rc != V2X_OK) return rc;
     return v2x_launch_splitk_reduce(a.ws, a.ksplit, (long long)a.N * (a.H / 2) * (a.W / 2), a.w_rows, a.Cout, a.scale, a.shift, a.relu, a.out,
                                     a.out_cstride, a.out_coff, s);
 }
@@ -892,14 +874,7 @@ static int launch_s2_splitk(const S2Args &a, hipStream_t s) {
 template <int BCO, int TH = S2_TH, int TW = S2_TW>
 static int launch_s2(const S2Args &a, hipStream_t s) {
     constexpr int smem = S2_RING * BCO * 64 + S2_PATCH_BYTES + 2 * BCO * 4;
-    static v2x_once_per_device attr_once;
-    auto kern = &conv3x3_s2_stream_kernel<BCO, TH, TW>;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
-    hipLaunchKernelGGL(kern, dim3(a.n_px_tiles * a.n_co_tiles), dim3(256), smem, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_s2_stream_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_s2_stream_kernel<BCO, TH, TW>>("conv3x3_s2_stream_kernel", dim3(a.n_px_tiles * a.n_co_tiles), dim3(256), smem, s, a);
 }
 
 // Returns V2X_OK if handled, 1 if the shape is not covered (caller reports).

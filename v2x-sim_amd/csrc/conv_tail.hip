@@ -409,15 +409,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 int v2x_num_cus();   // conv_stream.hip
 
 static int tail_launch(const TailArgs &a, hipStream_t s) {
-    static v2x_once_per_device attr_once;
-    if (v2x_first_use_on_device(attr_once))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, tail::SMEM);
     const int n_pairs = (a.n_tiles + 1) / 2;
     int grid = v2x_num_cus();
     if (grid > n_pairs) grid = n_pairs;
-    hipLaunchKernelGGL(conv3x3_tail_kernel, dim3(grid), dim3(512), tail::SMEM, s, a);
-    V2X_CHECK_LAUNCH("conv3x3_tail_kernel");
-    return V2X_OK;
+    return v2x_launch<conv3x3_tail_kernel>("conv3x3_tail_kernel", dim3(grid), dim3(512), tail::SMEM, s, a);
 }
 
 // v2x_conv2d_pair's second form (include/v2x_amd.h): first = conv8_2 (3x3 s1 p1, 32 -> 32, w_layout 1, bf16 NHWC input), second = the fused detection heads

@@ -452,29 +452,11 @@ extern "C" int v2x_conv3x3_wgrad(const uint16_t *x, const uint16_t *dy, int N, i
         V2X_REQUIRE(n_split >= 1 && n_split <= a.n_tiles, "v2x_conv3x3_wgrad: n_split=%d outside [1, %d]", n_split, a.n_tiles);
         a.n_split = n_split;
     }
-    static v2x_once_per_device attr_once;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_wgrad_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, WG_SMEM);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_wgrad_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, WG_SMEM);
-    }
     const int grid = (Cout / (rows32 ? 32 : WG_CO)) * (Cin / WG_CI) * a.n_split;
     if (v2x_tune(V2X_TUNE_WGRAD_TR) != 0) {   // the transpose-read form (default); 0: the first form (A/B, bitwise-equality test)
-        static v2x_once_per_device tr_once;
-        if (v2x_first_use_on_device(tr_once)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_wgrad_tr_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, WG_PX * 64 * 2 + WT_X_BYTES);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_wgrad_tr_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, WG_PX * 32 * 2 + WT_X_BYTES);
-        }
-        if (rows32)
-            hipLaunchKernelGGL(conv3x3_wgrad_tr_kernel<32>, dim3(grid), dim3(256), WG_PX * 32 * 2 + WT_X_BYTES, (hipStream_t)stream, a);
-        else
-            hipLaunchKernelGGL(conv3x3_wgrad_tr_kernel<64>, dim3(grid), dim3(256), WG_PX * 64 * 2 + WT_X_BYTES, (hipStream_t)stream, a);
-        V2X_CHECK_LAUNCH("conv3x3_wgrad_tr_kernel");
-        return V2X_OK;
+        if (rows32) return v2x_launch<conv3x3_wgrad_tr_kernel<32>>("conv3x3_wgrad_tr_kernel", dim3(grid), dim3(256), WG_PX * 32 * 2 + WT_X_BYTES, (hipStream_t)stream, a);
+        return v2x_launch<conv3x3_wgrad_tr_kernel<64>>("conv3x3_wgrad_tr_kernel", dim3(grid), dim3(256), WG_PX * 64 * 2 + WT_X_BYTES, (hipStream_t)stream, a);
     }
-    if (rows32)
-        hipLaunchKernelGGL(conv3x3_wgrad_kernel<32>, dim3(grid), dim3(256), WG_SMEM, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(conv3x3_wgrad_kernel<64>, dim3(grid), dim3(256), WG_SMEM, (hipStream_t)stream, a);
-    V2X_CHECK_LAUNCH("conv3x3_wgrad_kernel");
-    return V2X_OK;
+    if (rows32) return v2x_launch<conv3x3_wgrad_kernel<32>>("conv3x3_wgrad_kernel", dim3(grid), dim3(256), WG_SMEM, (hipStream_t)stream, a);
+    return v2x_launch<conv3x3_wgrad_kernel<64>>("conv3x3_wgrad_kernel", dim3(grid), dim3(256), WG_SMEM, (hipStream_t)stream, a);
 }

@@ -375,24 +375,20 @@ static int det_nms_launch(bool rotated, const float *loc_or_codes, const float *
                           int32_t *out_count, hipStream_t s) {
     const int smem_fast = NMS_FAST_CAP * 28 + NMS_FAST_CAP * (NMS_FAST_CAP / 64) * 8;   // 46 KiB: three workgroups per CU
     const int smem_full = cap * 28;   // keys 8 B + stand-up boxes 16 B + kept list 4 B per candidate
-    static v2x_once_per_device attr_once;
-    if (v2x_first_use_on_device(attr_once)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(det_nms_kernel<false, SLOTTED, false>), hipFuncAttributeMaxDynamicSharedMemorySize, DET_MAX_CAP * 28);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(det_nms_kernel<true, SLOTTED, false>), hipFuncAttributeMaxDynamicSharedMemorySize, DET_MAX_CAP * 28);
-    }
+    // (LDS opt-in: the full pass for the largest cap, whatever this launch's; the fast pass stays below 64 KiB and asks for none)
+    int rc;
     if (rotated) {
-        hipLaunchKernelGGL((det_nms_kernel<true, SLOTTED, true>), dim3(n), dim3(256), smem_fast, s, loc_or_codes, anchors, M, cap, nms_thr, keys, counts,
-                           out_boxes, out_scores, out_index, out_count, NMS_FAST_CAP, 0);
-        hipLaunchKernelGGL((det_nms_kernel<true, SLOTTED, false>), dim3(n), dim3(256), smem_full, s, loc_or_codes, anchors, M, cap, nms_thr, keys, counts,
-                           out_boxes, out_scores, out_index, out_count, cap, 1);
-    } else {
-        hipLaunchKernelGGL((det_nms_kernel<false, SLOTTED, true>), dim3(n), dim3(256), smem_fast, s, loc_or_codes, anchors, M, cap, nms_thr, keys, counts,
-                           out_boxes, out_scores, out_index, out_count, NMS_FAST_CAP, 0);
-        hipLaunchKernelGGL((det_nms_kernel<false, SLOTTED, false>), dim3(n), dim3(256), smem_full, s, loc_or_codes, anchors, M, cap, nms_thr, keys, counts,
-                           out_boxes, out_scores, out_index, out_count, cap, 1);
+        rc = v2x_launch<det_nms_kernel<true, SLOTTED, true>, 0>("det_nms_kernel", dim3(n), dim3(256), smem_fast, s, loc_or_codes, anchors, M, cap, nms_thr, keys, counts,
+                                                                out_boxes, out_scores, out_index, out_count, NMS_FAST_CAP, 0);
+        if (rc != V2X_OK) return rc;
+        return v2x_launch<det_nms_kernel<true, SLOTTED, false>, DET_MAX_CAP * 28>("det_nms_kernel", dim3(n), dim3(256), smem_full, s, loc_or_codes, anchors, M, cap, nms_thr,
+                                                                                  keys, counts, out_boxes, out_scores, out_index, out_count, cap, 1);
     }
-    V2X_CHECK_LAUNCH("det_nms_kernel");
-    return V2X_OK;
+    rc = v2x_launch<det_nms_kernel<false, SLOTTED, true>, 0>("det_nms_kernel", dim3(n), dim3(256), smem_fast, s, loc_or_codes, anchors, M, cap, nms_thr, keys, counts,
+                                                             out_boxes, out_scores, out_index, out_count, NMS_FAST_CAP, 0);
+    if (rc != V2X_OK) return rc;
+    return v2x_launch<det_nms_kernel<false, SLOTTED, false>, DET_MAX_CAP * 28>("det_nms_kernel", dim3(n), dim3(256), smem_full, s, loc_or_codes, anchors, M, cap, nms_thr,
+                                                                               keys, counts, out_boxes, out_scores, out_index, out_count, cap, 1);
 }
 
 static int det_postprocess_impl(bool rotated, const float *cls, const float *loc, const float *anchors, int n, int M,

@@ -422,17 +422,12 @@ extern "C" int v2x_voxelize_bits(const float *pts, const int32_t *n_pts, int n_c
     if (!lds_off && vp.Z <= 16 && lds_bytes <= 128 * 1024 && ((size_t)vp.X * vp.Y) % 8 == 0 && max_pts > 0 &&
         (reinterpret_cast<uintptr_t>(bits) & 15) == 0) {
         const bool vec4 = pt_stride == 4 && (reinterpret_cast<uintptr_t>(pts) & 15) == 0;
-        static v2x_once_per_device attr_once;
-        if (v2x_first_use_on_device(attr_once)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(voxelize_lds_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(voxelize_lds_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        }
+        // (LDS opt-in: the largest grid, whatever this launch's)
         if (vec4)
-            hipLaunchKernelGGL(voxelize_lds_kernel<true>, dim3(n_clouds), dim3(VOX_LDS_THREADS), lds_bytes, s, pts, n_pts, max_pts, pt_stride, vp, bits);
-        else
-            hipLaunchKernelGGL(voxelize_lds_kernel<false>, dim3(n_clouds), dim3(VOX_LDS_THREADS), lds_bytes, s, pts, n_pts, max_pts, pt_stride, vp, bits);
-        V2X_CHECK_LAUNCH("voxelize_lds_kernel");
-        return V2X_OK;
+            return v2x_launch<voxelize_lds_kernel<true>, 128 * 1024>("voxelize_lds_kernel", dim3(n_clouds), dim3(VOX_LDS_THREADS), (int)lds_bytes, s, pts, n_pts, max_pts,
+                                                                      pt_stride, vp, bits);
+        return v2x_launch<voxelize_lds_kernel<false>, 128 * 1024>("voxelize_lds_kernel", dim3(n_clouds), dim3(VOX_LDS_THREADS), (int)lds_bytes, s, pts, n_pts, max_pts,
+                                                                   pt_stride, vp, bits);
     }
     if (hipMemsetAsync(bits, 0, (size_t)n_clouds * vp.X * vp.Y * sizeof(uint32_t), s) != hipSuccess) {
         v2x_set_error("v2x_voxelize_bits: memset failed");
@@ -546,19 +541,11 @@ extern "C" int v2x_voxelize_fused_bits(const float *pts, const int32_t *n_pts, i
     const int lds_mode = v2x_tune(V2X_TUNE_VOXELIZE_LDS);
     if (lds_mode != 0 && !(lds_mode == 1 && n_grids <= 48) && vp.Z <= 16 && lds_bytes <= 128 * 1024 && ((size_t)vp.X * vp.Y) % 8 == 0 && max_pts > 0 &&
         n_jobs > 0) {
-        static v2x_once_per_device attr_once;
-        if (v2x_first_use_on_device(attr_once)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(voxelize_fused_lds_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(voxelize_fused_lds_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        }
         if (pt_stride == 4 && (reinterpret_cast<uintptr_t>(pts) & 15) == 0)
-            hipLaunchKernelGGL(voxelize_fused_lds_kernel<true>, dim3(n_grids), dim3(VOX_LDS_THREADS), lds_bytes, s, pts, n_pts, max_pts, pt_stride, xform,
-                               src_cloud, dst_grid, n_jobs, vp, bits, n_clouds);
-        else
-            hipLaunchKernelGGL(voxelize_fused_lds_kernel<false>, dim3(n_grids), dim3(VOX_LDS_THREADS), lds_bytes, s, pts, n_pts, max_pts, pt_stride, xform,
-                               src_cloud, dst_grid, n_jobs, vp, bits, n_clouds);
-        V2X_CHECK_LAUNCH("voxelize_fused_lds_kernel");
-        return V2X_OK;
+            return v2x_launch<voxelize_fused_lds_kernel<true>, 128 * 1024>("voxelize_fused_lds_kernel", dim3(n_grids), dim3(VOX_LDS_THREADS), (int)lds_bytes, s, pts, n_pts,
+                                                                            max_pts, pt_stride, xform, src_cloud, dst_grid, n_jobs, vp, bits, n_clouds);
+        return v2x_launch<voxelize_fused_lds_kernel<false>, 128 * 1024>("voxelize_fused_lds_kernel", dim3(n_grids), dim3(VOX_LDS_THREADS), (int)lds_bytes, s, pts, n_pts,
+                                                                         max_pts, pt_stride, xform, src_cloud, dst_grid, n_jobs, vp, bits, n_clouds);
     }
     if (hipMemsetAsync(bits, 0, (size_t)n_grids * vp.X * vp.Y * sizeof(uint32_t), s) != hipSuccess) {
         v2x_set_error("v2x_voxelize_fused_bits: memset failed");

@@ -114,6 +114,7 @@ SIGNATURES = {
     "v2x_conv_tile_rows": (C.c_int, [C.c_int, C.c_int]),
     "v2x_conv_stream_tile_rows": (C.c_int, [C.c_int, C.c_int]),
     "v2x_conv2d": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
+    "v2x_conv2d_plan": (C.c_int, [C.POINTER(ConvDesc), C.c_char_p, C.c_size_t]),
     "v2x_conv2d_pair": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.c_void_p]),
     "v2x_pack_codec_size": (C.c_longlong, [C.c_int, C.c_int, C.c_void_p]),
     "v2x_pack_codec": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 8),
@@ -201,3 +202,11 @@ def check(rc, what):
     if rc != 0:
         msg = load().v2x_last_error()
         raise V2XLibraryError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else "?"))
+
+
+def conv_plan(desc, what="v2x_conv2d_plan"):
+    """The kernel(s) v2x_conv2d would launch for this descriptor, as a profiler names them (a sequence joined with " + "): the library's own
+    dispatch run with the launch replaced by a record of the kernel's symbol.  Nothing is launched, no tensor is read, no GPU is needed."""
+    buf = C.create_string_buffer(512)
+    check(load().v2x_conv2d_plan(C.byref(desc), buf, len(buf)), what)
+    return buf.value.decode()

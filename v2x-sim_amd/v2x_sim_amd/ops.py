@@ -66,64 +66,38 @@ def latency_launches():
     return sb == 1 or (sb == 2 and getattr(_latency, "depth", 0) > 0)
 
 
-_CONV_TILES = {32: (32, 256, 1, 4), 48: (48, 256, 1, 4), 64: (64, 128, 2, 2), 128: (128, 128, 2, 2), 96: (96, 128, 2, 2)}
+def _conv_desc(pc, N, H, W):
+    """What the packed layer and the extent determine of a v2x_conv_desc; the caller adds the tensors."""
+    d = ConvDesc()
+    d.C0, d.C1, d.up0 = pc.C0, pc.C1, pc.up0
+    d.N, d.H, d.W = N, H, W
+    d.ksize, d.stride, d.pad = pc.ksize, pc.stride, pc.pad
+    d.Cout, d.w_rows, d.w_kpad = pc.Cout, pc.w_rows, pc.w_kpad
+    d.weight = pc.weight.data_ptr()
+    d.scale = pc.scale.data_ptr()
+    d.shift = pc.shift.data_ptr() if pc.shift is not None else None
+    d.epilogue, d.relu = pc.epilogue, int(bool(pc.relu))
+    d.w_layout = pc.w_layout or 0
+    if pc.Cout2:
+        d.Cout2, d.relu2 = pc.Cout2, int(bool(pc.relu2))
+        d.weight2, d.scale2, d.shift2 = pc.weight2.data_ptr(), pc.scale2.data_ptr(), pc.shift2.data_ptr()
+    return d
 
 
-def conv_kernel_name(pc, H=0, W=0, bits=False, N=0):
-    """Name of the template instantiation v2x_conv2d dispatches to (as rocprofv3 prints it)."""
-    if pc.w_layout == 2 and pc.stride == 2:
-        if pc.Cout == 64 and pc.C0 == 32:
-            return "conv3x3_s2_resident_kernel<64>"
-        rows = 128 if pc.Cout % 128 == 0 else 64
-        s2g = tuning.get("S2_G")
-        if rows == 128 and pc.C0 >= 64 and s2g != 0:       # conv_stream_s2.hip: v2x_conv_stream_s2_dispatch
-            Ho, Wo = H // 2, W // 2
-            g32 = Ho % 8 == 0 and Wo % 32 == 0
-            g16 = not g32 and Ho % 16 == 0 and Wo % 16 == 0
-            tiles = N * (Ho * Wo // 256) * (pc.Cout // 128)
-            if (g32 or g16) and not (latency_launches() and tiles < 4 * torch.cuda.get_device_properties(0).multi_processor_count):
-                return "conv3x3_s2g_kernel<%s>" % ("8, 32" if g32 else "16, 16")
-        if not (H % 8 == 0 and W % 64 == 0):
-            return "conv3x3_s2_stream_kernel<%d, 8, 16>" % rows    # 16 x 16 outputs (conv4_1)
-        return "conv3x3_s2_stream_kernel<%d, 4, 32>" % rows
-    if pc.w_layout == 2:
-        rows = _lib.load().v2x_conv_stream_tile_rows(pc.Cout, pc.epilogue)
-        th, tw = (8, 32) if W % 32 == 0 else (16, 16)
-        epi = 2 if pc.epilogue == V2X_EPI_GRU else (1 if pc.Cout2 else 0)
-        if W % 32 == 0 and H % 16 == 0 and rows == 64 and pc.epilogue == V2X_EPI_BF16 and (pc.C0 + pc.C1) >= 64 \
-                and tuning.get("STREAM_WIDE") != 0:
-            if epi == 0 and (pc.C0 + pc.C1) >= 96 and tuning.get("WIDE3") != 0:
-                return "conv3x3_wide3_kernel<64>"          # 128 pixels per wave, three taps per synchronisation
-            return "conv3x3_wide_kernel<64, %d>" % epi   # 128 pixels per wave (conv_stream.hip)
-        if W % 32 == 0 and H % 16 == 0 and rows in (96, 128) \
-                and tuning.get("STREAM_WAVES") != 4:
-            if epi != 1 and tuning.get("STREAM_G") != 0:
-                wt = tuning.get("STREAM_WT")   # wave tiling: half the channels x 128 pixels per wave
-                tiled = (wt >= 1 and epi == 0) or (wt >= 2 and epi == 2)
-                return "conv3x3_stream8g_kernel<%d, %d, %s>" % (rows, epi, "true" if tiled else "false")  # 8 waves, three taps per synchronisation
-            return "conv3x3_stream8_kernel<%d, %d>" % (rows, epi)  # 8-wave ping-pong form (conv_stream.hip)
-        return "conv3x3_stream_kernel<%d, %d, %d, %d, false>" % (rows, th, tw, epi)
-    if pc.w_layout == 4:
-        return "conv3x3_stream8q_kernel" if pc.Cout == 64 else "conv3x3_stream8p_kernel"   # streamed parity-class forms (conv7_1 | conv5_1, conv6_1)
-    if pc.w_layout == 3:
-        return "conv3x3_halo_ppc_kernel<%d, %d, %d>" % (pc.C0, pc.C1, pc.Cout)   # parity-class form (pre-summed 2x2-tap weights for the upsampled source)
-    if pc.w_layout == 1:
-        c0, c1 = (pc.C0, pc.C1) if pc.C1 else (0, pc.C0)
-        co2 = (pc.Cout2 + 15) // 16 * 16 if pc.Cout2 else 0
-        e2 = 0 if not pc.Cout2 else (2 if pc.epilogue == V2X_EPI_F32 else 1)
-        if (c0, c1, pc.Cout, co2) == (0, 32, 32, 0):  # HBM-bound layers: single-buffer form (+ bit-grid input)
-            return "conv3x3_halo_sb_kernel<0, 32, 32, 0, 0, %s>" % ("true" if bits else "false")
-        if (c0, c1, pc.Cout, co2, e2) == (0, 64, 64, 64, 1):
-            return "conv3x3_halo_pp_kernel<0, 64, 64, 64>"   # conv1_2 -> conv3d_1 chained: ping-pong form (odd tile counts: the 4-wave form)
-        if (c0, c1, pc.Cout, co2) in ((64, 32, 32, 0), (0, 64, 64, 0)) and tuning.get("HALO_PP") != 0:
-            return "conv3x3_halo_pp_kernel<%d, %d, %d, 0>" % (c0, c1, pc.Cout)   # conv8_1 / conv7_2: 8-wave ping-pong form
-        return "conv3x3_halo_kernel<%d, %d, %d, %d, %d>" % (c0, c1, pc.Cout, co2, e2)
-    if (pc.ksize == 1 and pc.stride == 1 and not pc.C1 and not pc.Cout2 and pc.epilogue in (V2X_EPI_BF16, V2X_EPI_F32) and pc.C0 % 32 == 0 and pc.C0 <= 128
-            and pc.C0 // 32 != 3 and 4 <= pc.Cout <= 128 and pc.Cout % 4 == 0 and (pc.Cout + 15) // 16 in (1, 2, 3, 4, 6, 8) and tuning.get("CONV1X1") != 0):
-        ks, ct = pc.C0 // 32, (pc.Cout + 15) // 16      # conv1x1.hip: the streaming 1x1 kernel (round 6; same bits as the gather kernel)
-        return "conv1x1_stream_kernel<%d, %d, %s, %d>" % (ks, ct, "true" if pc.epilogue == V2X_EPI_F32 else "false", 2 if ks * ct >= 16 else 4)
-    rows = _lib.load().v2x_conv_tile_rows(pc.Cout, pc.epilogue)
-    return "conv_igemm_kernel<%d, %d, %d, %d, %d>" % (_CONV_TILES[rows] + (pc.epilogue,))
+_NEVER_READ = 16   # placeholder address of conv_kernel_name's activations and output: non-null and 16-byte aligned as the dispatch asks, never dereferenced
+
+
+def conv_kernel_name(pc, H, W, bits=False, N=1):
+    """Name of the kernel v2x_conv2d launches for layer pc on N maps of H x W (the layer's full-resolution input extent), as rocprofv3 prints it:
+    asked of the library's own dispatch (v2x_conv2d_plan), nothing is launched.  The activations and the output are 16-byte aligned placeholders: the
+    answer is the one for aligned tensors (a misaligned 1x1 launch takes the gather kernel; conv2d's profiling branch asks with its real descriptor)."""
+    d = _conv_desc(pc, N, H, W)
+    d.in0, d.in1, d.out = _NEVER_READ, (_NEVER_READ if pc.C1 else None), _NEVER_READ
+    if bits:
+        d.in_format, d.in_zbits = 1, 1
+    d.out_cstride = pc.Cout2 or pc.Cout
+    d.small_batch = 1 if latency_launches() else 0
+    return _lib.conv_plan(d, "v2x_conv2d_plan(%s)" % pc.name)
 
 
 # ------------------------------------------------------------------ a1
@@ -292,20 +266,19 @@ def conv2d(pc, in0, in1=None, out=None, out_coff=0, split=0, zbits=0, splitk=0):
                     o1[sl].copy_(r[0])
                     o2[sl].copy_(r[1])
             return (o1, o2) if split else out
-    d = ConvDesc()
     from_bits = in0.dtype == torch.int32  # the voxelizer's bit grid (N, H, W): first layer, halo kernel only
     if from_bits:
         if pc.w_layout != 1 or in1 is not None or in0.dim() != 3 or not (1 <= zbits <= 32):
             raise ValueError("bit-grid input needs a halo-packed single-source layer and 1 <= zbits <= 32")
-        d.in0 = _dev(in0, torch.int32, "in0").value
-        d.in_format, d.in_zbits = 1, zbits
+        p_in0 = _dev(in0, torch.int32, "in0").value
         in0_shape = (in0.shape[0], in0.shape[1], in0.shape[2], pc.C0)
     else:
-        d.in0 = _dev(in0, torch.bfloat16, "in0").value
+        p_in0 = _dev(in0, torch.bfloat16, "in0").value
         in0_shape = tuple(in0.shape)
     N = in0.shape[0]
+    p_in1 = None
     if in1 is not None:
-        d.in1 = _dev(in1, torch.bfloat16, "in1").value
+        p_in1 = _dev(in1, torch.bfloat16, "in1").value
         H, W = in1.shape[1], in1.shape[2]
         if in1.shape[3] != pc.C1 or in1.shape[0] != N:
             raise ValueError("in1 shape %s does not match C1=%d" % (tuple(in1.shape), pc.C1))
@@ -314,7 +287,6 @@ def conv2d(pc, in0, in1=None, out=None, out_coff=0, split=0, zbits=0, splitk=0):
     else:
         if pc.C1:
             raise ValueError("layer %s expects a second source" % pc.name)
-        d.in1 = None
         H, W = in0.shape[1] << pc.up0, in0.shape[2] << pc.up0
     if in0_shape[3] != pc.C0:
         raise ValueError("in0 has %d channels, layer %s expects %d" % (in0_shape[3], pc.name, pc.C0))
@@ -329,22 +301,14 @@ def conv2d(pc, in0, in1=None, out=None, out_coff=0, split=0, zbits=0, splitk=0):
         out = torch.empty((N, Ho, Wo, cfin), dtype=odt, device=in0.device)
     elif tuple(out.shape[:3]) != (N, Ho, Wo):
         raise ValueError("out shape %s != %s" % (tuple(out.shape), (N, Ho, Wo, "*")))
-    d.C0, d.C1, d.up0 = pc.C0, pc.C1, pc.up0
-    d.N, d.H, d.W = N, H, W
-    d.ksize, d.stride, d.pad = pc.ksize, pc.stride, pc.pad
-    d.Cout, d.w_rows, d.w_kpad = pc.Cout, pc.w_rows, pc.w_kpad
-    d.weight = pc.weight.data_ptr()
-    d.scale = pc.scale.data_ptr()
-    d.shift = pc.shift.data_ptr() if pc.shift is not None else None
-    d.epilogue, d.relu = pc.epilogue, int(bool(pc.relu))
+    d = _conv_desc(pc, N, H, W)
+    d.in0, d.in1 = p_in0, p_in1
+    if from_bits:
+        d.in_format, d.in_zbits = 1, zbits
     d.out = _dev(out, odt, "out").value
     d.out_cstride, d.out_coff = out.shape[3], out_coff
     if split:
         d.out2, d.split, d.out2_cstride = out2.data_ptr(), split, out2.shape[3]
-    d.w_layout = pc.w_layout or 0
-    if pc.Cout2:
-        d.Cout2, d.relu2 = pc.Cout2, int(bool(pc.relu2))
-        d.weight2, d.scale2, d.shift2 = pc.weight2.data_ptr(), pc.scale2.data_ptr(), pc.shift2.data_ptr()
     ws = None
     if splitk > 1:
         ws = torch.empty((splitk, N * Ho * Wo, pc.w_rows), dtype=torch.float32, device=in0.device)
@@ -360,9 +324,7 @@ def conv2d(pc, in0, in1=None, out=None, out_coff=0, split=0, zbits=0, splitk=0):
         flops = 2.0 * M * (rows_logical * k_logical + (pc.Cout2 or 0) * pc.Cout)
         if pc.w_layout in (3, 4):   # parity-class forms: the FLOPs the kernel EXECUTES (4 taps on the upsampled source); the reference's 9-tap count is
             flops = 2.0 * M * pc.Cout * (4 * pc.C0 + 9 * pc.C1)   # reported separately (bench.py: reference_flops)
-        prof = _Prof(conv_kernel_name(pc, H, W, from_bits, N) if splitk <= 1 else
-                     "conv3x3_%sstream_kernel<%d, split-K %d> + splitk_reduce" % ("s2_" if pc.stride == 2 else "", lib.v2x_conv_stream_tile_rows(pc.Cout, pc.epilogue), splitk),
-                     flops, nbytes, pc.name)
+        prof = _Prof(_lib.conv_plan(d, "v2x_conv2d_plan(%s)" % pc.name), flops, nbytes, pc.name)   # the descriptor about to be launched
     rc = lib.v2x_conv2d(C.byref(d), _stream())
     if prof is not None:
         prof.done()
@@ -425,18 +387,6 @@ def codec_decompress(pc, msg):
     return y
 
 
-def _pair_desc(pc, N, H, W):
-    d = ConvDesc()
-    d.C0, d.C1, d.up0 = pc.C0, pc.C1, pc.up0
-    d.N, d.H, d.W = N, H, W
-    d.ksize, d.stride, d.pad = pc.ksize, pc.stride, pc.pad
-    d.Cout, d.w_rows, d.w_kpad = pc.Cout, pc.w_rows, pc.w_kpad
-    d.weight, d.scale, d.shift = pc.weight.data_ptr(), pc.scale.data_ptr(), pc.shift.data_ptr()
-    d.epilogue, d.relu = pc.epilogue, int(bool(pc.relu))
-    d.w_layout = pc.w_layout or 0
-    return d
-
-
 def pair_eligible(pa, pb, in0, zbits):
     """conv_halo_pair.hip covers: bit-grid input, two halo-packed 3x3 s1 32 -> 32 bf16 layers, H % 8 == 0, W % 32 == 0."""
     ok = lambda pc: (pc is not None and pc.w_layout == 1 and pc.ksize == 3 and pc.stride == 1 and pc.C0 == 32 and not pc.C1  # noqa: E731
@@ -451,7 +401,7 @@ def conv2d_pair(pa, pb, bits, zbits, out=None):
     N, H, W = bits.shape
     if out is None:
         out = torch.empty((N, H, W, pb.Cout), dtype=torch.bfloat16, device=bits.device)
-    da, db = _pair_desc(pa, N, H, W), _pair_desc(pb, N, H, W)
+    da, db = _conv_desc(pa, N, H, W), _conv_desc(pb, N, H, W)
     da.in0 = _dev(bits, torch.int32, "bits").value
     da.in_format, da.in_zbits = 1, zbits
     db.out = _dev(out, torch.bfloat16, "out").value
@@ -485,10 +435,8 @@ def conv2d_tail(pa, pb, x, split):
     N, H, W, _ = x.shape
     out = torch.empty((N, H, W, split), dtype=torch.float32, device=x.device)
     out2 = torch.empty((N, H, W, pb.Cout2 - split), dtype=torch.float32, device=x.device)
-    da, db = _pair_desc(pa, N, H, W), _pair_desc(pb, N, H, W)
+    da, db = _conv_desc(pa, N, H, W), _conv_desc(pb, N, H, W)
     da.in0 = _dev(x, torch.bfloat16, "x").value
-    db.Cout2, db.relu2 = pb.Cout2, int(bool(pb.relu2))
-    db.weight2, db.scale2, db.shift2 = pb.weight2.data_ptr(), pb.scale2.data_ptr(), pb.shift2.data_ptr()
     db.out, db.out_cstride, db.out_coff = out.data_ptr(), split, 0
     db.out2, db.split, db.out2_cstride = out2.data_ptr(), split, out2.shape[3]
     prof = None

@@ -62,7 +62,7 @@ def conv2d_det(pc, x, score_thr, cap=4096):
     prof = None
     if _launch.PROFILE is not None:
         M = N * H * W
-        prof = _Prof("conv3x3_halo_kernel<0, 32, 64, 64, 3>", 2.0 * M * (64 * 9 * 32 + 48 * 64), x.numel() * 2 + pc.weight.numel() * 2, pc.name)
+        prof = _Prof(_lib.conv_plan(d, "v2x_conv2d_plan(%s, det)" % pc.name), 2.0 * M * (64 * 9 * 32 + 48 * 64), x.numel() * 2 + pc.weight.numel() * 2, pc.name)
     rc = lib.v2x_conv2d(C.byref(d), _stream())
     if prof is not None:
         prof.done()
