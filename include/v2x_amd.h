@@ -453,6 +453,30 @@ int v2x_det_loss_backward(const float *cls, const float *labels, const float *lo
                           float alpha, float beta, const float *out4, const float *g_loss, const float *g_cls, const float *g_loc, float *dcls,
                           float *dloc, v2x_stream_t stream);
 
+/* Rows a8 / f-3, the segmentation loss of a training step, forward and backward (replaces the nn.CrossEntropyLoss of
+ * coperception/utils/SegModule.py::SegModule.step and its autograd backward -- not in /root/reference, README.md:101 names the scripts that call it;
+ * restated in v2x_sim_amd/train/loss.py::segmentation_loss): DEVICE fp32 logits [M][C] (NHWC, C % 4 == 0, 4 <= C <= 32, 16-byte aligned), labels
+ * [M] bytes, weight fp32 [C] or NULL (= 1).  A label >= C is ignored (255 by convention): w_i = label_i < C ? weight[label_i] : 0;
+ * num = sum w_i (logsumexp(logits_i) - logits_i[label_i]), den = sum w_i, out3 = {num / (den > 0 ? den : 1), num, den} -- F.cross_entropy(weight=,
+ * ignore_index=, reduction="mean") wherever den > 0, and 0 with zero gradients (not NaN) when every pixel is ignored.
+ * Forward = two launches (per-workgroup partials in workspace, added in workgroup order in fp64: bit-reproducible).
+ * Backward = d loss / d logit_ij = g w_i (softmax_ij - [j == label_i]) / den with g (g_loss: a DEVICE scalar, NULL = 1) and den (out3) read on the
+ * device, in two output forms over one per-pixel function -- the same values before rounding:
+ *   v2x_seg_loss_backward         one launch: dlogits fp32 [M][C];
+ *   v2x_seg_loss_backward_packed  two launches: what v2x_cast_pad_chsum_f32 would make of dlogits -- dy bf16 [M][Cp] (Cp by that entry's rules: Cp >= C,
+ *                                 Cp % 8 == 0, Cp / 8 divides 256; channels C..Cp-1 zero; bit-equal to the cast of the first form) and sums fp32 [C],
+ *                                 the per-channel sums of the fp32 gradients (the class head's bias gradient; fixed order: bit-reproducible).  The fp32
+ *                                 gradient is never stored.
+ * No atomics; every output is bit-reproducible.  workspace: v2x_seg_loss_workspace_size(M, C, Cp) bytes covers the forward and the packed backward
+ * (Cp = 0: the forward alone); 0 = unsupported shape. */
+long long v2x_seg_loss_workspace_size(long long M, int C, int Cp);
+int v2x_seg_loss_forward(const float *logits, const uint8_t *labels, const float *weight, long long M, int C, float *out3, float *workspace,
+                         v2x_stream_t stream);
+int v2x_seg_loss_backward(const float *logits, const uint8_t *labels, const float *weight, long long M, int C, const float *out3, const float *g_loss,
+                          float *dlogits, v2x_stream_t stream);
+int v2x_seg_loss_backward_packed(const float *logits, const uint8_t *labels, const float *weight, long long M, int C, const float *out3,
+                                 const float *g_loss, int Cp, uint16_t *dy, float *sums, float *workspace, v2x_stream_t stream);
+
 /* ---------------------------------------------------------------- f-3: the cross-agent warp of the TRAINING graph, forward and data gradient
  * Replaces F.affine_grid + F.grid_sample(mode="bilinear", padding_mode="zeros", align_corners=False) of
  * coperception/models/det/base/IntermediateModelBase.py::feature_transformation (applied twice there: rotation, then translation) and its

@@ -112,7 +112,94 @@ def main():
     for k, (n, t) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
         print("  %-58s x%-3d %9.1f" % (k, n, t))
     print("  total %.1f ms in %d launches" % (sum(v[1] for v in agg.values()) / 1e3, sum(v[0] for v in agg.values())))
+    seg_section()
+
+
+def _paired(fns, rounds=7, reps=20):
+    """{name: fn} timed round-robin in one process (box and clock drift cancel) -> {name: (median us, min us)}."""
+    times = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            times[k].append(timed(fn, reps))
+    return {k: (sorted(t)[len(t) // 2], min(t)) for k, t in times.items()}
+
+
+def seg_section(frames=2, agents=5):
+    """Segmentation training (rows a8 / f-3): csrc/seg_loss.hip against the PyTorch ops at the 10-map extent, its packed backward against the fp32 form +
+    v2x_cast_pad_chsum_f32, and SegModule.step -- today's eager step against the captured one -- for FaFNetSeg and V2VNetSeg at 10 maps."""
+    from v2x_sim_amd import ops
+    dev = torch.device("cuda:0")
+    M, C = frames * agents * 256 * 256, 8
+    g = torch.Generator().manual_seed(0)
+    logits = (torch.randn(M, C, generator=g) * 3).to(dev)
+    lab = torch.randint(0, C, (M,), generator=g)
+    lab[torch.rand(M, generator=g) < 0.1] = 255
+    lab8, lab64 = lab.to(torch.uint8).to(dev), lab.to(dev)
+    one = torch.ones((), device=dev)
+
+    def torch_ops():
+        x = logits.detach().requires_grad_(True)
+        F.cross_entropy(x, lab64, ignore_index=255).backward()
+
+    def torch_ops_head():       # ... and what _Conv1x1.backward then does to the fp32 gradient
+        x = logits.detach().requires_grad_(True)
+        F.cross_entropy(x, lab64, ignore_index=255).backward()
+        ops.cast_pad_chsum(x.grad, 32)
+
+    def hip_a():
+        out3 = ops.seg_loss_forward(logits, lab8)
+        return ops.seg_loss_backward(logits, lab8, None, out3, one)
+
+    out3 = ops.seg_loss_forward(logits, lab8)
+
+    def form_a_then_pack():
+        ops.cast_pad_chsum(ops.seg_loss_backward(logits, lab8, None, out3, one), 32)
+
+    def form_b():
+        ops.seg_loss_backward_packed(logits, lab8, None, out3, one, 32)
+    print("segmentation loss, %d pixels x %d classes (us, median of 7 rounds x 20, paired; min):" % (M, C))
+    for k, (med, lo) in _paired({"F.cross_entropy forward + backward (PyTorch ops)": torch_ops, "v2x_seg_loss_forward + _backward": hip_a,
+                                 "backward (a) + v2x_cast_pad_chsum_f32 (Cp 32)": form_a_then_pack, "v2x_seg_loss_backward_packed (Cp 32)": form_b,
+                                 "PyTorch ops + v2x_cast_pad_chsum_f32": torch_ops_head}).items():
+        print("  %-52s %9.1f  (min %.1f)" % (k, med, lo))
+    # the step: SegModule.step as it stands (switches 0, a plain Adam) against the captured step (the three switches on, a capturable Adam)
+    sys.path.insert(0, os.path.join(ROOT, "tools", "seg"))
+    from train_seg import seg_batch
+    from v2x_sim_amd.configs import Config
+    from v2x_sim_amd.models.seg import FaFNetSeg, V2VNetSeg
+    from v2x_sim_amd.train.loop import init_for_training
+    from v2x_sim_amd.utils.SegModule import SegModule
+    cfg = Config("train", binary=True, only_det=True)
+    data = seg_batch(cfg, frames, agents, 1, dev, ops.VoxelGrid(cfg.voxel_size, cfg.area_extents))
+    data["labels"] = data["labels"].to(torch.uint8)
+    tuning.set("TRAIN_HIP", 1)
+    names = ("TRAIN_SEG_LOSS_HIP", "TRAIN_SEG_HEAD_FUSE", "TRAIN_SEG_GRAPH")
+    for cls in (FaFNetSeg, V2VNetSeg):
+        res = {}
+        for label, sw, capt in (("eager, switches 0 (the step as it was)", (0, 0, 0), False), ("eager, loss kernels + fused head", (1, 1, 0), False),
+                                ("captured (one hipGraph)", (1, 1, 1), True)):
+            for n, v in zip(names, sw):
+                tuning.set(n, v)
+            model = init_for_training(cls(cfg, num_agent=agents), seed=0).to(dev)
+            opt = (torch.optim.Adam(model.parameters(), lr=torch.tensor(1e-4, device=dev), capturable=True) if capt else torch.optim.Adam(model.parameters(), lr=1e-4))
+            module = SegModule(model, None, cfg, opt, 0)
+            for _ in range(3):
+                module.step(data, agents, frames)
+            torch.cuda.synchronize()
+            t = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    module.step(data, agents, frames)
+                torch.cuda.synchronize()
+                t.append((time.perf_counter() - t0) / 10 * 1e3)
+            res[label] = (sorted(t)[2], min(t))
+        for n in names:
+            tuning.set(n, 0)
+        print("%s training step (SegModule.step: fwd + loss + bwd + Adam + loss.item()), %d maps (ms wall, median of 5 x 10; min):" % (cls.__name__, frames * agents))
+        for k, (med, lo) in res.items():
+            print("  %-52s %8.2f  (min %.2f)" % (k, med, lo))
 
 
 if __name__ == "__main__":
-    main()
+    seg_section() if sys.argv[1:2] == ["seg"] else main()

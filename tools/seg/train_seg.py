@@ -46,11 +46,23 @@ def build_parser():
     ap.add_argument("--resume", default="", type=str)
     from v2x_sim_amd.utils import comm
     comm.add_arguments(ap)
+    ap.add_argument("--engine", default="", choices=["", "torch", "hip", "hip-graph"],
+                    help="training graph: torch = PyTorch-ROCm ops (fp32, MIOpen); hip = bf16 NHWC graph on the hand-written kernels (V2X_TRAIN_HIP=1), the loss "
+                         "as PyTorch ops; hip-graph = the same with the loss kernels, the class head fused with the loss and every step replayed as one hipGraph "
+                         "(V2X_TRAIN_SEG_LOSS_HIP / _HEAD_FUSE / _GRAPH = 1; a capturable Adam with a device-tensor learning rate).  Default: whatever the "
+                         "environment variables say")
+    ap.add_argument("--class_weight", default="", type=str, help="comma list of per-class loss weights (the kernel loss paths; default: none)")
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.engine:
+        from v2x_sim_amd import tuning
+        tuning.set("TRAIN_HIP", int("0" if args.engine == "torch" else "1"))
+        for name in ("TRAIN_SEG_LOSS_HIP", "TRAIN_SEG_HEAD_FUSE", "TRAIN_SEG_GRAPH"):
+            tuning.set(name, int("1" if args.engine == "hip-graph" else "0"))
+    class_weight = [float(v) for v in args.class_weight.split(",")] if args.class_weight else None
     from v2x_sim_amd import ops
     from v2x_sim_amd.configs import Config
     from v2x_sim_amd.models.seg import FaFNetSeg, V2VNetSeg
@@ -84,13 +96,18 @@ def main(argv=None):
                             generator=torch.Generator().manual_seed(args.seed))
         print("training on %d frames x %d agents from %s" % (len(dataset), A, args.data))
     # one optimizer for the whole run, kept in the checkpoint (same rule as tools/det/train_codet.py)
-    opt = torch.optim.Adam(model.parameters(), lr=args.lr)
+    if args.engine == "hip-graph":       # the captured step needs the step counters and the learning rate on the device
+        opt = torch.optim.Adam(model.parameters(), lr=torch.tensor(args.lr, dtype=torch.float32, device=device), capturable=True)
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     start = 1
     if ckpt is not None and "optimizer_state_dict" in ckpt:
         opt.load_state_dict(ckpt["optimizer_state_dict"])
     if ckpt is not None and "epoch" in ckpt:
         start = int(ckpt["epoch"]) + 1
-    module = SegModule(model, None, config, opt, 0)
+    if class_weight is not None and len(class_weight) != model.n_classes:
+        raise SystemExit("--class_weight needs %d values" % model.n_classes)
+    module = SegModule(model, None, config, opt, 0, class_weight=class_weight)
     grid = ops.VoxelGrid(config.voxel_size, config.area_extents)
     for epoch in range(start, args.nepoch + 1):
         losses = []

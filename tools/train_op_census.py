@@ -19,7 +19,7 @@ from v2x_sim_amd.models.det import FaFNet, V2VNet  # noqa: E402
 from v2x_sim_amd.train import detection_loss, train_forward  # noqa: E402
 from v2x_sim_amd.train.loop import init_for_training, synthetic_batch_on_device  # noqa: E402
 
-OURS = ("conv3x3_", "conv1x1_", "bn_", "wgrad_", "upcat_", "cast_pad_", "channel_sum", "det_loss", "pack_conv", "zero_insert", "dense_f32", "warp_affine", "gru_", "voxel",
+OURS = ("conv3x3_", "conv1x1_", "bn_", "wgrad_", "upcat_", "cast_pad_", "channel_sum", "det_loss", "seg_loss", "pack_conv", "zero_insert", "dense_f32", "warp_affine", "gru_", "voxel",
         "conv_igemm", "conv_gather", "adam_", "splitk_reduce", "v2v_", "vt_sum", "warp_fuse", "attn_", "seg_")
 
 

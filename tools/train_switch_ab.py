@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Paired timing of the training-step switches (row f-3): one captured step per switch setting, replays interleaved round-robin in ONE process (box and clock
-drift cancel).  usage: python tools/train_switch_ab.py [FaFNet|V2VNet] [frames] [SETTING ...]   with SETTING = NAME=v[,NAME=v...] (tuning switches; "default" = none
+drift cancel).  usage: python tools/train_switch_ab.py [FaFNet|V2VNet|FaFNetSeg|V2VNetSeg] [frames] [SETTING ...]   with SETTING = NAME=v[,NAME=v...] (tuning switches; "default" = none
 changed); without settings: TRAIN_PACK_BATCH=0 against TRAIN_PACK_BATCH=1 (round 4's comparison)."""
 import copy
 import os
@@ -21,8 +21,20 @@ from v2x_sim_amd.train.loop import init_for_training, synthetic_batch_on_device 
 def main(family="FaFNet", frames=2, settings=("TRAIN_PACK_BATCH=0", "TRAIN_PACK_BATCH=1"), agents=5, rounds=5, reps=20):
     dev = torch.device("cuda:0")
     cfg = Config("train")
-    data = synthetic_batch_on_device(cfg, frames, agents, seed=1, device=dev)
-    cls, kw = (FaFNet, dict(kd_flag=0, num_agent=agents)) if family == "FaFNet" else (V2VNet, dict(num_agent=agents))
+    seg = family.endswith("Seg")
+    if seg:       # the segmentation variants: GraphedSegTrainStep over a tools/seg/train_seg.py batch (TRAIN_SEG_LOSS_HIP / TRAIN_SEG_HEAD_FUSE are read at capture)
+        sys.path.insert(0, os.path.join(ROOT, "tools", "seg"))
+        from train_seg import seg_batch
+        from v2x_sim_amd import ops
+        from v2x_sim_amd.models.seg import FaFNetSeg, V2VNetSeg
+        from v2x_sim_amd.train.graph_step import GraphedSegTrainStep
+        cfg = Config("train", binary=True, only_det=True)
+        data = seg_batch(cfg, frames, agents, 1, dev, ops.VoxelGrid(cfg.voxel_size, cfg.area_extents))
+        cls, kw, step_cls = (FaFNetSeg if family == "FaFNetSeg" else V2VNetSeg), dict(num_agent=agents), GraphedSegTrainStep
+    else:
+        data = synthetic_batch_on_device(cfg, frames, agents, seed=1, device=dev)
+        cls, kw = (FaFNet, dict(kd_flag=0, num_agent=agents)) if family == "FaFNet" else (V2VNet, dict(num_agent=agents))
+        step_cls = GraphedTrainStep
     base = init_for_training(cls(cfg, **kw), seed=0).to(dev).train()
     tuning.set("TRAIN_HIP", 1)
     steps = {}
@@ -35,7 +47,7 @@ def main(family="FaFNet", frames=2, settings=("TRAIN_PACK_BATCH=0", "TRAIN_PACK_
         hip_graph._PLANS.clear()
         m = copy.deepcopy(base)
         opt = torch.optim.Adam(m.parameters(), lr=torch.tensor(1e-4, device=dev), capturable=True, fused=True)
-        steps[setting] = GraphedTrainStep(m, opt, data, frames)      # the switches are read while the step is captured: the graph keeps its kernels
+        steps[setting] = step_cls(m, opt, data, frames)      # the switches are read while the step is captured: the graph keeps its kernels
         for k, v in saved.items():
             tuning.set(k, v)
     times = {k: [] for k in steps}

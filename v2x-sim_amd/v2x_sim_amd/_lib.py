@@ -89,6 +89,10 @@ SIGNATURES = {
     "v2x_det_loss_workspace_size": (C.c_longlong, [C.c_longlong]),
     "v2x_det_loss_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_longlong, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "v2x_det_loss_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_longlong, C.c_float, C.c_float] + [C.c_void_p] * 7),
+    "v2x_seg_loss_workspace_size": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
+    "v2x_seg_loss_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v2x_seg_loss_backward": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong, C.c_int] + [C.c_void_p] * 4),
+    "v2x_seg_loss_backward_packed": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     "v2x_pack_conv_device_job": (C.c_int, [C.POINTER(PackSpec), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(PackJob), C.POINTER(C.c_int64)]),
     "v2x_pack_conv_device_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "v2x_channel_sum_workspace_size": (C.c_longlong, [C.c_longlong, C.c_int]),

@@ -674,7 +674,7 @@ from .ops_post import conv2d_det, det_nms_candidates, det_postprocess, match_det
 from .ops_track import assign_iou, sort_step  # noqa: E402,F401
 from .ops_train import (bn_train_backward, bn_train_forward, cast_pad_chsum, channel_sum, conv3x3_wgrad, det_loss_backward, det_loss_forward,  # noqa: E402,F401
                         gru_gates, gru_gates_backward, gru_gates_nhwc, gru_gates_nhwc_backward, gru_gates_nhwc_ok, upcat, upcat_backward, v2v_message,
-                        v2v_message_backward, warp_affine, zero_insert)
+                        seg_loss_backward, seg_loss_backward_packed, seg_loss_forward, seg_loss_shape_ok, v2v_message_backward, warp_affine, zero_insert)
 
 
 # `ops.PROFILE = []` / `ops.PROFILE` (bench.py, tools/): one list for every wrapper module, kept in _launch

@@ -143,6 +143,74 @@ def det_loss_backward(cls, labels, loc, targets, mask, alpha, beta, out4, g_loss
     return dcls, dloc
 
 
+def _seg_loss_operands(logits, labels, weight, c_pad=0):
+    """-> (M, C) when the segmentation-loss kernels take these operands (fp32 contiguous device logits (..., C), C % 4 == 0, 4 <= C <= 32; uint8 labels, one per
+    pixel; fp32 weight (C,) or None; c_pad by v2x_cast_pad_chsum_f32's rules), else None."""
+    Cc = logits.shape[-1] if logits.dim() else 0
+    if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and labels.dtype == torch.uint8 and labels.is_contiguous()
+            and labels.device == logits.device and Cc >= 4):
+        return None
+    M = logits.numel() // Cc
+    if labels.numel() != M or (weight is not None and not (weight.dtype == torch.float32 and weight.numel() == Cc and weight.is_contiguous()
+                                                            and weight.device == logits.device)):
+        return None
+    if _lib.load().v2x_seg_loss_workspace_size(M, Cc, c_pad) == 0:
+        return None
+    return M, Cc
+
+
+def seg_loss_shape_ok(M, C, c_pad=0):
+    """Whether the segmentation-loss kernels take M pixels x C classes (and, c_pad != 0, the packed backward with that padded channel count)."""
+    return _lib.load().v2x_seg_loss_workspace_size(M, C, c_pad) > 0
+
+
+def seg_loss_forward(logits, labels, weight=None):
+    """v2x_seg_loss_forward: logits (..., C) fp32 NHWC, labels (...) uint8 (a label >= C is ignored), weight (C,) fp32 or None -> out3 (3,) fp32 =
+    (loss, num, den): train/loss.py::segmentation_loss.  None for operands the kernels do not take (the caller's PyTorch-op path)."""
+    mc = _seg_loss_operands(logits, labels, weight)
+    if mc is None:
+        return None
+    lib = _lib.load()
+    M, Cc = mc
+    ws = torch.empty((lib.v2x_seg_loss_workspace_size(M, Cc, 0) // 4,), dtype=torch.float32, device=logits.device)
+    out = torch.empty((3,), dtype=torch.float32, device=logits.device)
+    _lib.check(lib.v2x_seg_loss_forward(_dev(logits, torch.float32, "logits"), _dev(labels, torch.uint8, "labels"), _dev_opt(weight, torch.float32, "weight"), M, Cc,
+                                        _dev(out, torch.float32, "out3"), _dev(ws, torch.float32, "workspace"), _stream()), "v2x_seg_loss_forward")
+    return out
+
+
+def seg_loss_backward(logits, labels, weight, out3, g_loss=None):
+    """v2x_seg_loss_backward: -> dlogits fp32 like logits for the incoming gradient of the loss (an fp32 device scalar; None = 1); None as above."""
+    mc = _seg_loss_operands(logits, labels, weight)
+    if mc is None:
+        return None
+    M, Cc = mc
+    d = torch.empty_like(logits)
+    _lib.check(_lib.load().v2x_seg_loss_backward(_dev(logits, torch.float32, "logits"), _dev(labels, torch.uint8, "labels"), _dev_opt(weight, torch.float32, "weight"), M, Cc,
+                                                 _dev(out3, torch.float32, "out3"), _dev_opt(g_loss, torch.float32, "g_loss"), _dev(d, torch.float32, "dlogits"), _stream()),
+               "v2x_seg_loss_backward")
+    return d
+
+
+def seg_loss_backward_packed(logits, labels, weight, out3, g_loss, c_pad):
+    """v2x_seg_loss_backward_packed: -> (bf16 (..., c_pad) gradients with channels C.. zero, (C,) fp32 per-channel sums of the fp32 gradients) -- what
+    cast_pad_chsum makes of seg_loss_backward's result, in one pass over the logits.  None as above."""
+    if c_pad <= 0:
+        return None
+    mc = _seg_loss_operands(logits, labels, weight, c_pad)
+    if mc is None:
+        return None
+    lib = _lib.load()
+    M, Cc = mc
+    ws = torch.empty((lib.v2x_seg_loss_workspace_size(M, Cc, c_pad) // 4,), dtype=torch.float32, device=logits.device)
+    dy = torch.empty(logits.shape[:-1] + (c_pad,), dtype=torch.bfloat16, device=logits.device)
+    sums = torch.empty((Cc,), dtype=torch.float32, device=logits.device)
+    _lib.check(lib.v2x_seg_loss_backward_packed(_dev(logits, torch.float32, "logits"), _dev(labels, torch.uint8, "labels"), _dev_opt(weight, torch.float32, "weight"), M, Cc,
+                                                _dev(out3, torch.float32, "out3"), _dev_opt(g_loss, torch.float32, "g_loss"), c_pad, _dev(dy, torch.bfloat16, "dy"),
+                                                _dev(sums, torch.float32, "sums"), _dev(ws, torch.float32, "workspace"), _stream()), "v2x_seg_loss_backward_packed")
+    return dy, sums
+
+
 def channel_sum(x):
     """x (..., C) bf16 NHWC -> (C,) fp32 = the sum over every other axis, in a fixed order (the bias gradient of a convolution)."""
     lib = _lib.load()

@@ -16,6 +16,8 @@ _KEYS = ("bev_seq", "labels", "reg_targets", "reg_loss_mask", "trans_matrices")
 
 
 class GraphedTrainStep:
+    _keys = _KEYS          # the batch entries copied into static tensors (GraphedSegTrainStep: its own)
+
     def __init__(self, model, optimizer, data, batch_size, warmup=3, normalizer="positives"):
         """model on the MI355X in train mode; optimizer: torch.optim.Adam(..., capturable=True) (lr may be a device tensor, see set_lr) or one without host-side state (plain SGD);
         data: one batch in FaFModule.step's format -- its shapes are the shapes of every later batch."""
@@ -29,7 +31,7 @@ class GraphedTrainStep:
         use_hip_adam(optimizer)          # (a plain torch.optim.Adam steps on the library's kernel: train/optim.py)
         self.model, self.optimizer, self.batch_size = model, optimizer, batch_size
         self.normalizer = normalizer     # configs.Config.loss_normalizer (oracle/ASSUMPTIONS.md row 49)
-        self.static = {k: data[k].clone() for k in _KEYS if data.get(k) is not None}
+        self.static = {k: data[k].clone() for k in self._keys if data.get(k) is not None}
         self.num_agent = None if data.get("num_agent") is None else data["num_agent"].clone().cpu()
         self._forward = train_forward
         model.train()
@@ -105,3 +107,32 @@ class GraphedTrainStep:
         for g in self.optimizer.param_groups:
             packing.note_params_changed(g["params"])
         return self.losses
+
+
+_SEG_KEYS = ("bev_seq", "labels", "trans_matrices")
+
+
+class GraphedSegTrainStep(GraphedTrainStep):
+    """The segmentation variants' step (utils/SegModule.py::SegModule.step with TRAIN_SEG_GRAPH) as one hipGraph: the same capture, warm-up, scope rules and
+    replay as the detection step above -- FaFNetSeg always, V2VNetSeg for the `num_agent` table it was captured with -- over the static inputs bev_seq,
+    labels (uint8) and trans_matrices; the step body is hip_graph.seg_train_loss (class head + loss: csrc/seg_loss.hip), backward, optimizer.
+    __call__ -> the loss, a device scalar (valid until the next call)."""
+    _keys = _SEG_KEYS
+
+    def __init__(self, model, optimizer, data, batch_size, warmup=3, class_weight=None, ignore_index=255):
+        if not hasattr(model, "outc"):
+            raise ValueError("GraphedSegTrainStep needs a segmentation variant (a model with an `outc` class head)")
+        dev = data["bev_seq"].device
+        self.class_weight = None if class_weight is None else torch.as_tensor(class_weight, dtype=torch.float32, device=dev).contiguous()
+        self.ignore_index = ignore_index
+        super().__init__(model, optimizer, dict(data, labels=data["labels"].to(torch.uint8)), batch_size, warmup=warmup)
+
+    def _step_body(self):
+        from .hip_graph import seg_train_loss
+        s = self.static
+        loss = seg_train_loss(self.model, s["bev_seq"], s["labels"], s.get("trans_matrices"), self.num_agent, self.batch_size,
+                              weight=self.class_weight, ignore_index=self.ignore_index)
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        self.optimizer.step()
+        return loss.detach()

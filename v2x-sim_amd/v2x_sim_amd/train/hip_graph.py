@@ -688,6 +688,80 @@ def _fused_on_fp32_graph(fuse, model, feat, *args):
     return (out.permute(0, 2, 3, 1).to(dtype=BF16, memory_format=torch.contiguous_format),) + tuple(extra)
 
 
+def _seg_decoder_output(model, x, T, num_agent_tensor, batch_size):
+    """The segmentation variants up to the decoder output (N, H, W, 32) bf16: the map the 1x1 class head reads."""
+    if hasattr(model, "stpn"):
+        return decoder(model.stpn.decoder, *encoder(model.stpn.encoder, x))
+    feats = encoder(model.u_encoder, x)
+    feats[model.layer] = _v2v_stage(model, feats[model.layer], T, num_agent_tensor, batch_size)
+    return decoder(model.decoder, *feats)
+
+
+class _SegHeadLoss(torch.autograd.Function):
+    """The 1x1 class head and the segmentation loss as ONE autograd node (TRAIN_SEG_HEAD_FUSE): forward = the head (fp32 logits) + the loss' two launches;
+    backward = the loss' gradient in the form the head's gradient kernels read (csrc/seg_loss.hip form (b): bf16, channels padded to 32, the bias gradient
+    on the side -- the fp32 logit gradient and _Conv1x1.backward's pass over it never exist), then the same data- / weight-gradient calls as _Conv1x1."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, labels, class_weight):
+        ctx.set_materialize_grads(False)
+        logits = ops.conv2d(_layer_1x1("fwd", weight, bias, True, 0), x)
+        out = ops.seg_loss_forward(logits, labels, class_weight)
+        ctx.save_for_backward(x, weight, logits, labels, out, *(() if class_weight is None else (class_weight,)))
+        ctx.has_bias = bias is not None
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None
+        x, weight, logits, labels, out = ctx.saved_tensors[:5]
+        class_weight = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else None
+        cout = weight.shape[0]
+        cp = (cout + 31) // 32 * 32
+        dyp, sums = ops.seg_loss_backward_packed(logits, labels, class_weight, out, g.to(torch.float32).contiguous(), cp)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.conv2d(_layer_1x1("dgrad", weight, None, False, cp), dyp)
+        if ctx.needs_input_grad[1]:
+            dw = ops.conv3x3_wgrad(x, dyp)[:cout, :, 1, 1].reshape(weight.shape)
+        db = sums if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        return dx, dw, db, None, None
+
+
+def seg_head_loss(y, weight, bias, labels, class_weight=None, ignore_index=255):
+    """Class head + loss on a decoder-shaped bf16 NHWC map y: the fused node where the extent and the class count are ones the kernels take (and
+    TRAIN_SEG_HEAD_FUSE and TRAIN_SEG_LOSS_HIP are on), else conv1x1 + train/loss.py::segmentation_loss."""
+    from .loss import seg_loss_weight, segmentation_loss
+    N, H, W, cin = y.shape
+    cout = weight.shape[0]
+    if (tuning.get("TRAIN_SEG_HEAD_FUSE") != 0 and tuning.get("TRAIN_SEG_LOSS_HIP") != 0 and y.dtype == BF16 and H % 8 == 0 and W % 32 == 0 and cin % 32 == 0
+            and labels.dtype == torch.uint8 and labels.device == y.device and tuple(labels.shape) == (N, H, W) and ignore_index >= cout
+            and ops.seg_loss_shape_ok(N * H * W, cout, (cout + 31) // 32 * 32)):
+        return _SegHeadLoss.apply(y.contiguous(), weight, bias, labels.contiguous(), seg_loss_weight(class_weight, y))
+    return segmentation_loss(conv1x1(y, weight, bias, f32_out=True), labels, class_weight, ignore_index)
+
+
+def seg_train_loss(model, bevs, labels, trans_matrices=None, num_agent_tensor=None, batch_size=1, weight=None, ignore_index=255):
+    """One forward pass of a segmentation variant to its LOSS: the seg branch of _train_forward up to the decoder output, then seg_head_loss.
+    bevs (A*B, 1, X, Y, Z) on the MI355X, labels (A*B, X, Y) -> the scalar loss (model.training must be on)."""
+    if not hasattr(model, "outc"):
+        raise ValueError("seg_train_loss: a segmentation variant (a model with an `outc` class head) is needed")
+    if not bevs.is_cuda:
+        raise RuntimeError("train/hip_graph.py runs on the MI355X (no CPU path)")
+    prev, _DEFER_COUNTERS[0] = _DEFER_COUNTERS[0], True
+    _repack_stale()
+    _rezero_arena()
+    try:
+        T = None if trans_matrices is None else trans_matrices.to(bevs.device)
+        y = _seg_decoder_output(model, nhwc_input(bevs), T, num_agent_tensor, batch_size)
+        return seg_head_loss(y, model.outc.conv.weight, model.outc.conv.bias, labels, weight, ignore_index)
+    finally:
+        _DEFER_COUNTERS[0] = prev
+        if not prev:
+            _flush_counters()
+
+
 def train_forward(model, bevs, trans_matrices=None, num_agent_tensor=None, batch_size=1, inference="softmax"):
     """See _train_forward; the BatchNorm layers' num_batches_tracked counters are bumped together, in one launch, when the forward is complete."""
     prev, _DEFER_COUNTERS[0] = _DEFER_COUNTERS[0], True
@@ -712,12 +786,7 @@ def _train_forward(model, bevs, trans_matrices=None, num_agent_tensor=None, batc
     x = nhwc_input(bevs)
     T = None if trans_matrices is None else trans_matrices.to(x.device)
     if hasattr(model, "outc"):                      # segmentation variants: det backbone + 1x1 head, NHWC fp32 logits
-        if hasattr(model, "stpn"):
-            y = decoder(model.stpn.decoder, *encoder(model.stpn.encoder, x))
-        else:
-            feats = encoder(model.u_encoder, x)
-            feats[model.layer] = _v2v_stage(model, feats[model.layer], T, num_agent_tensor, batch_size)
-            y = decoder(model.decoder, *feats)
+        y = _seg_decoder_output(model, x, T, num_agent_tensor, batch_size)
         return conv1x1(y, model.outc.conv.weight, model.outc.conv.bias, f32_out=True)
     if hasattr(model, "stpn"):                      # FaFNet: lowerbound / upperbound
         return heads(model, decoder(model.stpn.decoder, *encoder(model.stpn.encoder, x)))

@@ -5,6 +5,9 @@
   localisation:   smooth-L1 (sigma = 3  ->  beta = 1/9) over the anchors selected by reg_loss_mask,
   both summed and divided by the number of positive anchors (at least 1);  loss = cls + loc.
   normalizer="batch" (oracle/ASSUMPTIONS.md row 49, the second reading; configs.Config.loss_normalizer): divided by the number of maps instead.
+
+Segmentation loss of upstream coperception/utils/SegModule.py::SegModule.step (nn.CrossEntropyLoss; absent from /root/reference as well), restated as
+segmentation_loss: pixel-wise softmax cross entropy with optional class weights and ignored labels, the weighted mean over the pixels that count.
 """
 import torch
 import torch.nn.functional as F
@@ -78,3 +81,77 @@ def detection_loss(result, labels, reg_targets, reg_loss_mask, normalizer="posit
                            beta=1.0 / (SIGMA * SIGMA))
     loc_loss = (per * m).sum() / n_pos
     return cls_loss + loc_loss, cls_loss, loc_loss
+
+
+class _SegLossHip(torch.autograd.Function):
+    """segmentation_loss on the hand-written kernels (csrc/seg_loss.hip): forward = one pass over logits and labels + a finish launch, backward = one pass
+    writing the fp32 logit gradients (form (a); the class head fused with the loss takes form (b): train/hip_graph.py::_SegHeadLoss)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight):
+        from .. import ops
+        ctx.set_materialize_grads(False)
+        out = ops.seg_loss_forward(logits, labels, weight)
+        ctx.save_for_backward(logits, labels, out, *(() if weight is None else (weight,)))
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        from .. import ops
+        if g_loss is None:
+            return None, None, None
+        logits, labels, out = ctx.saved_tensors[:3]
+        weight = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        return ops.seg_loss_backward(logits, labels, weight, out, g_loss.to(torch.float32).contiguous()), None, None
+
+
+def seg_loss_weight(weight, logits):
+    """The class weights as the kernels take them: None, or an fp32 contiguous (C,) tensor on the logits' device."""
+    if weight is None:
+        return None
+    return torch.as_tensor(weight, dtype=torch.float32, device=logits.device).contiguous()
+
+
+def _hip_seg_loss_ok(logits, labels, weight):
+    from .. import tuning
+    if not (logits.is_cuda and tuning.get("TRAIN_HIP") != 0 and tuning.get("TRAIN_SEG_LOSS_HIP") != 0):
+        return False
+    if logits.dtype != torch.float32 or labels.dtype != torch.uint8 or labels.device != logits.device:
+        return False
+    return seg_kernels_take(logits, labels, weight)
+
+
+def seg_kernels_take(logits, labels, weight, c_pad=0):
+    """Whether csrc/seg_loss.hip takes these operands (contiguous forms of them): C % 4 == 0, 4 <= C <= 32, one label per pixel."""
+    from .. import ops_train
+    return ops_train._seg_loss_operands(logits.contiguous(), labels.contiguous(), weight, c_pad) is not None
+
+
+def segmentation_loss(logits, labels, weight=None, ignore_index=255):
+    """logits (..., C) fp32 NHWC, labels (...) uint8 (or any integer type on the PyTorch-op path), weight (C,) or None  ->  the scalar loss
+
+        valid_i = label_i < C                 (every label >= C is ignored; ignore_index, 255 by convention, must be one of them)
+        w_i     = valid_i * (weight[label_i] or 1),   nll_i = logsumexp(logits_i) - logits_i[label_i]
+        loss    = sum w_i nll_i / (sum w_i if sum w_i > 0 else 1)
+
+    which is F.cross_entropy(weight=, ignore_index=, reduction="mean") wherever a pixel counts, and 0 with zero gradients (not NaN) where none does.
+    On the MI355X with TRAIN_HIP and TRAIN_SEG_LOSS_HIP != 0, fp32 logits and uint8 labels: three launches of csrc/seg_loss.hip; otherwise the PyTorch ops
+    below (the specification): masked sums, no data-dependent shape -- no host synchronisation, capturable in a hipGraph (train/graph_step.py)."""
+    Cn = logits.shape[-1]
+    if not (ignore_index >= Cn or ignore_index < 0):
+        raise ValueError("segmentation_loss: ignore_index %d names a class of the %d-class head" % (ignore_index, Cn))
+    if tuple(labels.shape) != tuple(logits.shape[:-1]):
+        raise ValueError("segmentation_loss: labels %s do not match logits %s" % (tuple(labels.shape), tuple(logits.shape)))
+    w = None if weight is None else torch.as_tensor(weight, device=logits.device)
+    if _hip_seg_loss_ok(logits, labels, None if w is None else w.to(torch.float32).contiguous()):
+        return _SegLossHip.apply(logits.contiguous(), labels.contiguous(), seg_loss_weight(w, logits))
+    lab = labels.reshape(-1).long()
+    x = logits.reshape(-1, Cn)
+    valid = (lab >= 0) & (lab < Cn)
+    safe = torch.where(valid, lab, torch.zeros_like(lab))
+    wi = valid.to(x.dtype)
+    if w is not None:
+        wi = wi * w.to(x.dtype)[safe]
+    nll = torch.logsumexp(x, dim=-1) - x.gather(1, safe[:, None])[:, 0]
+    num, den = (wi * nll).sum(), wi.sum()
+    return num / torch.where(den > 0, den, torch.ones_like(den))

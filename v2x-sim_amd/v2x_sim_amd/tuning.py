@@ -47,13 +47,21 @@ Host-side switches (this module):
                    forward, four backward per round) when every frame of the batch has the same number of agents; 0: the fp32 NCHW graph around the warp / gates kernels
     TRAIN_ADAM_HIP 1  a plain torch.optim.Adam handed to FaFModule / SegModule / make_optimizer / GraphedTrainStep steps on v2x_adam_step_f32 (train/optim.py: same state,
                    same update; one launch per 72 tensors); 0: torch's own step
+    TRAIN_SEG_LOSS_HIP 0  with TRAIN_HIP: the segmentation loss (train/loss.py::segmentation_loss: class weights, ignored labels) and its gradient as three launches of
+                   csrc/seg_loss.hip, and SegModule.step's eager step through it; 0: SegModule.step's F.cross_entropy / the PyTorch ops that are its specification
+    TRAIN_SEG_HEAD_FUSE 0  with TRAIN_SEG_LOSS_HIP: the 1x1 class head and the loss as one autograd node (train/hip_graph.py::_SegHeadLoss) -- the loss' backward writes
+                   the head's bf16 channel-padded gradient operand and the bias gradient directly (v2x_seg_loss_backward_packed); 0: fp32 gradients + v2x_cast_pad_chsum_f32
+    TRAIN_SEG_GRAPH 0  with TRAIN_HIP: SegModule.step replays the whole step as ONE hipGraph (train/graph_step.py::GraphedSegTrainStep) under TRAIN_GRAPH's conditions --
+                   FaFNetSeg always, V2VNetSeg while the agent table equals the captured one, a capturable optimizer; 0: always eager
+                   (first measurements: profiles/seg_train_bench.txt -- a 10-map step 7.5 -> 3.7 / 4.3 ms captured; the three default to 0 for now, so every caller runs the step it ran before)
     TRAIN_HIP_CONV 0  only the eligible 3x3 layers of the fp32 graph on the kernels (the first step of row f-3, kept for its tests)
 Retired in round 6 (their alternate forms had been measured slower for two rounds or more and no test or tool exercised them): S2_RESIDENT, S2_T16, PP_64, UPCAT_HIP.
 The tests use the `tune` fixture (tests/conftest.py), which restores every value it touched."""
 import ctypes as C
 import os
 
-_HOST_DEFAULTS = {"CONV_PAIR": 1, "TRAIN_HIP": 1, "TRAIN_GRAPH": 1, "TRAIN_HIP_CONV": 0, "SMALL_BATCH": 2, "WARP_HIP": 1, "WARP_XCD": 1, "SEG_FUSE": 1, "TRAIN_PACK_BATCH": 1, "TRAIN_LOSS_HIP": 1, "TRAIN_GATES_HIP": 1, "PARITY_CLASS": 3, "TAIL_FUSE": 1, "TRAIN_HEAD_PACK": 1, "TRAIN_BN_BIAS_ZERO": 1, "TRAIN_UPCAT_CONV": 1, "TRAIN_SPLITK": 480, "TRAIN_V2V_NHWC": 1, "TRAIN_ADAM_HIP": 1, "SPLITK_TARGET": 320}
+_HOST_DEFAULTS = {"CONV_PAIR": 1, "TRAIN_HIP": 1, "TRAIN_GRAPH": 1, "TRAIN_HIP_CONV": 0, "SMALL_BATCH": 2, "WARP_HIP": 1, "WARP_XCD": 1, "SEG_FUSE": 1, "TRAIN_PACK_BATCH": 1, "TRAIN_LOSS_HIP": 1, "TRAIN_GATES_HIP": 1, "PARITY_CLASS": 3, "TAIL_FUSE": 1, "TRAIN_HEAD_PACK": 1, "TRAIN_BN_BIAS_ZERO": 1, "TRAIN_UPCAT_CONV": 1, "TRAIN_SPLITK": 480, "TRAIN_V2V_NHWC": 1, "TRAIN_ADAM_HIP": 1, "SPLITK_TARGET": 320,
+                  "TRAIN_SEG_LOSS_HIP": 0, "TRAIN_SEG_HEAD_FUSE": 0, "TRAIN_SEG_GRAPH": 0}
 LIBRARY_SWITCHES = ("STREAM_WAVES", "STREAM_G", "STREAM_WT", "STORE_X4", "STREAM_PERSIST", "STREAM_WIDE", "WIDE3", "HALO_PP",
                     "VOXELIZE_LDS", "WARP_LDS", "S2_G", "GRU_XCD_WALK", "HALO_XCD", "WGRAD_TR", "BN_PARTIAL_T", "WGRAD_REDUCE4", "CONV1X1")
 
