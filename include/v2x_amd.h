@@ -576,7 +576,8 @@ int v2x_det_nms_candidates(const unsigned long long *keys, const float *codes, c
 /* ---------------------------------------------------------------- f-1: the metric (coperception/utils/mean_ap.py::eval_map)
  * Upstream intersects shapely polygons on the host; here the IoU of rotated boxes (x, y, w, h, yaw) is a convex clip in
  * fp64 on the device.
- * v2x_rotated_iou: boxes_a fp32 [na][5], boxes_b fp32 [nb][5] -> iou fp32 [na][nb]. */
+ * v2x_rotated_iou: boxes_a fp32 [na][5], boxes_b fp32 [nb][5] -> iou fp32 [na][nb].  Extents w, h >= 0: a rectangle of zero width or
+ * height has IoU 0 with everything (itself included); a negative or NaN extent is out of contract (the result is unspecified). */
 int v2x_rotated_iou(const float *boxes_a, int na, const float *boxes_b, int nb, float *iou, v2x_stream_t stream);
 /* v2x_match_detections: eval_map's per-image matching (mmdet tpfp_default).  det_boxes fp32 [n_img][det_cap][5] in DESCENDING
  * score order (what v2x_det_postprocess emits), det_count int32 [n_img]; gt_boxes fp32 [n_img][gt_cap][5], gt_count int32

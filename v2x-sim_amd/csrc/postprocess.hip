@@ -78,6 +78,10 @@ __device__ double quad_intersection_area(const double (&ax)[4], const double (&a
 }
 
 __device__ double rotated_iou_d(const float *a, const float *b) {
+    // A rectangle without area shares none with anything.  Not only a shortcut: all four edges of a POINT rectangle (w = h = 0) have
+    // zero length, every sp below is 0 and "inside", so clipping against it returned the whole of `a` -- inter = area(a) up to its
+    // rounding, uni = a rounding error, IoU = 0 or ~1e16 as the rounding fell.
+    if ((double)a[2] * a[3] == 0.0 || (double)b[2] * b[3] == 0.0) return 0.0;
     double ax[4], ay[4], bx[4], by[4];
     box_corners_d(a, ax, ay);
     box_corners_d(b, bx, by);
