@@ -617,6 +617,24 @@ int v2x_assign_iou(const float *iou, const int32_t *n_rows, const int32_t *n_col
 int v2x_sort_step(const float *det_boxes, const int32_t *det_count, int n, int det_cap, int box_format, float *trk_f, int32_t *trk_i,
                   int32_t *stream_i, int t_cap, float iou_thr, int max_age, int min_hits, int direct, float *out_boxes, int32_t *out_ids,
                   int32_t *out_det, int32_t *out_count, v2x_stream_t stream);
+/* v2x_hota_sequences: the HOTA family (TrackEval's hota.py) of n_seq padded sequences in FIVE launches whatever n_seq and
+ * n_frames are, no host round trip (capturable), no atomics: the result does not depend on the schedule, and a sequence's rows do not depend on
+ * the padding or on the other sequences of the call.
+ * gt_boxes fp32 [n_seq][n_frames][cap][4] (x1, y1, x2, y2; 16-byte aligned), gt_ids int32 [n_seq][n_frames][cap], gt_count int32
+ *   [n_seq][n_frames] (clamped to [0, cap]); trk_boxes, trk_ids, trk_count the same for the tracks.  cap in [1, 64].  Ids are per sequence and
+ *   contiguous, 0 .. n_gt_ids - 1 / 0 .. n_trk_ids - 1 (the largest id spaces of the call); a box whose id lies outside is absent everywhere.
+ *   An id twice in one frame is a caller error: unspecified result, memory-safe and terminating.
+ * Similarity = the IoU of the axis-aligned boxes in fp64, a NaN or infinite value reads as 0.
+ * alpha: DEVICE fp64 [n_alpha], n_alpha in [1, 32]: the thresholds (a matched pair counts for alpha when S >= alpha - 2^-52).
+ * workspace: DEVICE, 16-byte aligned, workspace_bytes >= v2x_hota_workspace_size(the same six sizes) (0: sizes out of range or an overflow); it
+ *   needs no initialisation and holds nothing the caller needs afterwards.
+ * OUTPUT per sequence and alpha: out_i int32 [n_seq][n_alpha][3] = TP, FN, FP; out_f fp64 [n_seq][n_alpha][4] = AssA, AssRe, AssPr and the
+ *   sum of the matched similarities (LocA = that sum / TP).  DetA, DetRe, DetPr, HOTA and the combination over sequences follow from these on the
+ *   host (v2x_sim_amd/utils/mot_metrics.py::Hota).  n_seq x n_frames and n_seq x n_gt_ids x ceil(n_trk_ids / 64) <= 2^24. */
+size_t v2x_hota_workspace_size(int n_seq, int n_frames, int cap, int n_gt_ids, int n_trk_ids, int n_alpha);
+int v2x_hota_sequences(const float *gt_boxes, const int32_t *gt_ids, const int32_t *gt_count, const float *trk_boxes, const int32_t *trk_ids,
+                       const int32_t *trk_count, int n_seq, int n_frames, int cap, int n_gt_ids, int n_trk_ids, const double *alpha, int n_alpha,
+                       void *workspace, size_t workspace_bytes, int32_t *out_i, double *out_f, v2x_stream_t stream);
 
 /* ---------------------------------------------------------------- d: calibration probes (measurement)
  * No upstream counterpart.  The roofline fractions bench.py prints are graded against the datasheet peaks (8 TB/s, 2.5 PFLOP/s bf16);

@@ -1,12 +1,16 @@
-"""Row f-5 (tracking): python wrappers over v2x_assign_iou and v2x_sort_step (csrc/track.hip).  Re-exported by ops.py (`ops.sort_step` ...)."""
+"""Row f-5 (tracking): python wrappers over v2x_assign_iou and v2x_sort_step (csrc/track.hip) and v2x_hota_sequences (csrc/hota.hip).  Re-exported by
+ops.py (`ops.sort_step` ...)."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
 from ._launch import _dev, _stream
 
 TRACK_CAP = 64      # tracks per stream, detections read per map, rows / columns of a matrix: one wave
+HOTA_MAX_ALPHA = 32
+HOTA_ALPHAS = np.arange(0.05, 0.99, 0.05)      # TrackEval's 19 thresholds, numpy's exact float64 values
 
 
 def assign_iou(iou, n_rows, n_cols, thr=0.3, direct=True):
@@ -46,3 +50,34 @@ def sort_step(det_boxes, det_count, trk_f, trk_i, stream_i, out=None, box_format
                                  _dev(ids, torch.int32, "out_ids"), _dev(det, torch.int32, "out_det"), _dev(count, torch.int32, "out_count"), _stream()),
                "v2x_sort_step")
     return out
+
+
+def hota_sequences(gt_boxes, gt_ids, gt_count, trk_boxes, trk_ids, trk_count, n_gt_ids, n_trk_ids, alpha=None):
+    """The HOTA counts of S padded sequences in ONE library call (five launches, no host synchronisation).
+    gt_boxes (S, F, cap, 4) fp32 xyxy, gt_ids (S, F, cap) int32, gt_count (S, F) int32, the same for the tracks, cap <= 64; ids per sequence in
+    [0, n_gt_ids) / [0, n_trk_ids); alpha: (n_alpha,) float64 on the device or None for HOTA_ALPHAS.
+    -> out_i (S, n_alpha, 3) int32 = TP, FN, FP; out_f (S, n_alpha, 4) float64 = AssA, AssRe, AssPr, the sum of the matched similarities."""
+    lib = _lib.load()
+    S, F, cap, four = gt_boxes.shape
+    if four != 4 or tuple(trk_boxes.shape) != (S, F, cap, 4):
+        raise ValueError("gt_boxes and trk_boxes must both be (S, F, cap, 4), got %s and %s" % (tuple(gt_boxes.shape), tuple(trk_boxes.shape)))
+    for name, t, shape in (("gt_ids", gt_ids, (S, F, cap)), ("trk_ids", trk_ids, (S, F, cap)), ("gt_count", gt_count, (S, F)), ("trk_count", trk_count, (S, F))):
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must be %s, got %s" % (name, shape, tuple(t.shape)))
+    dev = gt_boxes.device
+    if alpha is None:
+        alpha = torch.from_numpy(HOTA_ALPHAS).to(dev)
+    n_alpha = alpha.numel()
+    nbytes = lib.v2x_hota_workspace_size(S, F, cap, int(n_gt_ids), int(n_trk_ids), n_alpha)
+    if nbytes == 0:
+        raise ValueError("hota_sequences: S = %d, F = %d, cap = %d, n_gt_ids = %d, n_trk_ids = %d, n_alpha = %d out of range (F >= 1, cap in [1, %d], n_alpha in "
+                         "[1, %d])" % (S, F, cap, n_gt_ids, n_trk_ids, n_alpha, TRACK_CAP, HOTA_MAX_ALPHA))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    out_i = torch.empty((S, n_alpha, 3), dtype=torch.int32, device=dev)
+    out_f = torch.empty((S, n_alpha, 4), dtype=torch.float64, device=dev)
+    _lib.check(lib.v2x_hota_sequences(_dev(gt_boxes, torch.float32, "gt_boxes"), _dev(gt_ids, torch.int32, "gt_ids"), _dev(gt_count, torch.int32, "gt_count"),
+                                      _dev(trk_boxes, torch.float32, "trk_boxes"), _dev(trk_ids, torch.int32, "trk_ids"),
+                                      _dev(trk_count, torch.int32, "trk_count"), S, F, cap, int(n_gt_ids), int(n_trk_ids),
+                                      _dev(alpha, torch.float64, "alpha"), n_alpha, _dev(ws, torch.uint8, "workspace"), nbytes,
+                                      _dev(out_i, torch.int32, "out_i"), _dev(out_f, torch.float64, "out_f"), _stream()), "v2x_hota_sequences")
+    return out_i, out_f

@@ -7,7 +7,12 @@ The assignment runs on `ops.assign_iou` (the tracker's own association kernel). 
 continuity-preferred pairs FIRST, not by scaling (1000 + IoU in fp32 would leave 14 bits of the IoU): a GT has at most one previous tracker id
 and a tracker id at most one GT, so the continuity pairs above the threshold form a partial matching by themselves, and because one bonus
 outweighs any sum of IoUs (<= 64) every optimum of TrackEval's score contains all of them (replacing the two pairs that block one loses < 2 and
-wins > 1000).  They are fixed, their rows and columns zeroed, and the kernel assigns the rest on the thresholded IoUs: the same optimum."""
+wins > 1000).  They are fixed, their rows and columns zeroed, and the kernel assigns the rest on the thresholded IoUs: the same optimum.
+
+The HOTA family (`Hota`; TrackEval's hota.py) is frame-independent once the global alignment score is known, so it is NOT scored
+frame by frame: `update` only collects, `result` pads every sequence to one shape and makes ONE `ops.hota_sequences` call (csrc/hota.hip, five launches)
+for all of them; what remains on the host is the arithmetic on 19 x 7 numbers per sequence."""
+import numpy as np
 import torch
 
 from .. import ops_track
@@ -86,3 +91,99 @@ class ClearMot(object):
         gt = self.tp + self.fn
         return {"MOTA": (self.tp - self.fp - self.idsw) / gt if gt else 0.0, "MOTP": self.iou_sum / self.tp if self.tp else 0.0,
                 "IDSW": self.idsw, "TP": self.tp, "FP": self.fp, "FN": self.fn}
+
+
+HOTA_FIELDS = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA")
+
+
+def _hota_fields(tp, fn, fp, loc, ass_a, ass_re, ass_pr, alphas):
+    """Per-alpha arrays of one sequence or of a combination -> the result record (scalars = means over alpha)."""
+    tpf, fnf, fpf = tp.astype(np.float64), fn.astype(np.float64), fp.astype(np.float64)
+    det_a = tpf / np.maximum(1, tpf + fnf + fpf)
+    per = {"HOTA": np.sqrt(det_a * ass_a), "DetA": det_a, "AssA": ass_a, "DetRe": tpf / np.maximum(1, tpf + fnf), "DetPr": tpf / np.maximum(1, tpf + fpf),
+           "AssRe": ass_re, "AssPr": ass_pr, "LocA": np.maximum(1e-10, loc) / np.maximum(1e-10, tpf), "TP": tp, "FN": fn, "FP": fp, "loc": loc}
+    out = {k: float(np.mean(per[k])) for k in HOTA_FIELDS + ("TP", "FN", "FP")}
+    out["alphas"] = alphas
+    out["per_alpha"] = per
+    return out
+
+
+class Hota(object):
+    """update(gt_boxes (G, 4), gt_ids (G,), trk_boxes (T, 4), trk_ids (T,)) adds one frame to the current sequence (boxes x1, y1, x2, y2 on the device,
+    read as float32; ids host integers of any value, unique within the frame; G, T <= 64), new_sequence() closes it.
+    result() -> HOTA, DetA, AssA, DetRe, DetPr, AssRe, AssPr, LocA and TP, FN, FP as means over the thresholds, "alphas", "per_alpha" (the same
+    fields and the matched-similarity sum "loc" as arrays), and "sequences": the same record for every sequence.  Sequences combine as TrackEval
+    combines them: counts and loc add, AssA / AssRe / AssPr are TP-weighted means, the detection fields and HOTA are recomputed."""
+
+    def __init__(self, alphas=None):
+        self.alphas = np.array(ops_track.HOTA_ALPHAS if alphas is None else alphas, dtype=np.float64).reshape(-1)
+        self._closed = []
+        self._frames = []
+
+    def update(self, gt_boxes, gt_ids, trk_boxes, trk_ids):
+        if not gt_boxes.is_cuda or not trk_boxes.is_cuda:
+            raise RuntimeError("Hota runs on the MI355X (cuda) device; the v2x_sim_amd hot path has no CPU fallback")
+        gt_ids = [int(g) for g in (gt_ids.tolist() if torch.is_tensor(gt_ids) else gt_ids)]
+        trk_ids = [int(t) for t in (trk_ids.tolist() if torch.is_tensor(trk_ids) else trk_ids)]
+        cap = ops_track.TRACK_CAP
+        if len(gt_ids) > cap or len(trk_ids) > cap:
+            raise ValueError("Hota takes at most %d ground-truth boxes and %d tracks per frame" % (cap, cap))
+        if len(set(gt_ids)) != len(gt_ids) or len(set(trk_ids)) != len(trk_ids):
+            raise ValueError("Hota: an id occurs twice in one frame")
+        self._frames.append((gt_boxes.reshape(len(gt_ids), 4).to(torch.float32), gt_ids, trk_boxes.reshape(len(trk_ids), 4).to(torch.float32), trk_ids))
+
+    def new_sequence(self):
+        self._closed.append(self._frames)
+        self._frames = []
+
+    def padded(self):
+        """Every sequence padded to one shape, ids renumbered per sequence in order of first appearance: the arguments of ops.hota_sequences --
+        (gt_boxes, gt_ids, gt_count, trk_boxes, trk_ids, trk_count, n_gt_ids, n_trk_ids), or None without a sequence."""
+        seqs = self._closed + ([self._frames] if self._frames else [])
+        if not seqs:
+            return None
+        S = len(seqs)
+        F = max([len(q) for q in seqs] + [1])
+        cap = max([max(len(fr[1]), len(fr[3])) for q in seqs for fr in q] + [1])
+        ids = np.zeros((2, S, F, cap), dtype=np.int32)
+        count = np.zeros((2, S, F), dtype=np.int32)
+        n_ids = [0, 0]
+        boxes, dest = ([], []), ([], [])                    # per side: the frames' box tensors and their rows in the padded array
+        for s, q in enumerate(seqs):
+            remap = ({}, {})
+            for f, fr in enumerate(q):
+                for side in (0, 1):
+                    b, i = fr[2 * side], fr[2 * side + 1]
+                    n = len(i)
+                    ids[side, s, f, :n] = [remap[side].setdefault(v, len(remap[side])) for v in i]
+                    count[side, s, f] = n
+                    if n:
+                        boxes[side].append(b)
+                        dest[side].append((s * F + f) * cap + np.arange(n))
+            n_ids = [max(n_ids[side], len(remap[side])) for side in (0, 1)]
+        dev = next((b[0].device for b in boxes if b), torch.device("cuda", torch.cuda.current_device()))
+        padded = []
+        for side in (0, 1):
+            p = torch.zeros((S * F * cap, 4), dtype=torch.float32, device=dev)
+            if boxes[side]:
+                p[torch.from_numpy(np.concatenate(dest[side])).to(dev)] = torch.cat(boxes[side])
+            padded.append(p.view(S, F, cap, 4))
+        ids_d, count_d = torch.from_numpy(ids).to(dev), torch.from_numpy(count).to(dev)
+        return padded[0], ids_d[0], count_d[0], padded[1], ids_d[1], count_d[1], n_ids[0], n_ids[1]
+
+    def result(self):
+        args = self.padded()
+        A = len(self.alphas)
+        S = 0 if args is None else args[0].shape[0]
+        tp, fn, fp = (np.zeros((S, A), dtype=np.int64) for _ in range(3))
+        ass, loc = np.zeros((S, A, 3)), np.zeros((S, A))
+        if S:
+            out_i, out_f = ops_track.hota_sequences(*args, alpha=torch.from_numpy(self.alphas).to(args[0].device))
+            out_i, out_f = out_i.cpu().numpy().astype(np.int64), out_f.cpu().numpy()
+            tp, fn, fp = out_i[..., 0], out_i[..., 1], out_i[..., 2]
+            ass, loc = out_f[..., :3], out_f[..., 3]
+        tps = np.maximum(1, tp.sum(0))
+        w = [(ass[..., k] * tp).sum(0) / tps for k in range(3)]
+        out = _hota_fields(tp.sum(0), fn.sum(0), fp.sum(0), loc.sum(0), w[0], w[1], w[2], self.alphas)
+        out["sequences"] = [_hota_fields(tp[s], fn[s], fp[s], loc[s], ass[s, :, 0], ass[s, :, 1], ass[s, :, 2], self.alphas) for s in range(S)]
+        return out
