@@ -185,7 +185,6 @@ __global__ __launch_bounds__(LDSW ? 512 : 256) void codec_kernel(const CodecArgs
     }
 }
 
-int v2x_num_cus();   // conv_stream.hip
 
 static inline bool codec_cc_ok(int C, int Cc) { return Cc >= 1 && Cc < C && (Cc & (Cc - 1)) == 0; }
 

@@ -38,6 +38,7 @@ enum v2x_tune_id {
     V2X_TUNE_COUNT
 };
 int v2x_tune(int id);
+int v2x_num_cus();   // compute units of the current device (conv_stream.hip): the persistent grids' size
 
 #define V2X_REQUIRE(cond, ...)            \
     do {                                  \

@@ -111,7 +111,6 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(const C1Args a) {
     }
 }
 
-int v2x_num_cus();   // conv_stream.hip
 
 template <int KS, int CT, bool F32>
 static int launch_c1(const C1Args &a, hipStream_t s) {

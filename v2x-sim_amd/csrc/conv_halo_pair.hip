@@ -336,7 +336,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
-int v2x_num_cus();   // conv_stream.hip
 
 // first: 3x3 s1 p1, bit-grid input (in_format 1), 32 (padded) -> 32, w_layout 1, bf16 epilogue; second: 32 -> 32 likewise.
 // The intermediate map is never stored: first->out is ignored.

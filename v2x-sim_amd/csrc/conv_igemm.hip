@@ -23,6 +23,7 @@
 //     and padding taps read a zero page.  Two stages, one barrier per chunk; the DMA of chunk
 //     t+1 is issued before the MFMAs of chunk t.
 #include "common.h"
+#include "stream_geom.h"
 
 struct ConvArgs {
     const uint16_t *in0, *in1;
@@ -75,15 +76,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {
     const int wco = wave / WPX;
     const int wpx = wave % WPX;
 
-    // XCD-aware tile order (guide T1): workgroup b runs on XCD b%8; give every XCD a contiguous run
-    // of tiles so the channel tiles of one pixel tile (same activations) and neighbouring pixel
-    // tiles (shared halos) hit the same L2.  Bijective for any grid size.
-    const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, i = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
+    const int bid = xcd_major_bid(blockIdx.x, gridDim.x);   // XCD-major tile order (stream_geom.h)
     const int n_co_tiles = a.w_rows / BCO;
     const int co_tile = bid % n_co_tiles;
     const int px_tile = bid / n_co_tiles;

@@ -1,7 +1,8 @@
 // Declarations of the streamed-weights kernel families of conv_stream.hip (4-wave, 8-wave ping-pong, wide forms): kernel arguments, LDS / LDS-DMA
-// helpers, patch geometry.
+// helpers, and -- shared with conv_stream_pc.hip, conv_stream_s2.hip -- the patch tables and DMA issue on top of the geometry of stream_geom.h.
 #pragma once
 #include "common.h"
+#include "stream_geom.h"
 
 typedef const __attribute__((address_space(1))) void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;
@@ -61,4 +62,47 @@ enum { SEPI_BF16 = 0, SEPI_CHAIN = 1, SEPI_GRU = 2 };
 constexpr int PATCH8_PIECES = 40;            // 18 x 34 pixels x 64 B = 38.25 KiB; piece 39 is padding / dummy target
 constexpr int PATCH8_BYTES = PATCH8_PIECES * 1024;
 
-int v2x_num_cus();
+// counted wait: at most N vector-memory operations (LDS-DMAs, stores) of this wave still in flight
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// lane id from VOLATILE asm: values derived from it cannot be hoisted out of the tile / chunk / step loops (as lane constants they would be --
+// dozens of registers kept, and spilled, across the MFMA phases); they are recomputed where they are used
+__device__ __forceinline__ int fresh_lane() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+
+// per-lane column-offset table ct[c][kx] (stream_geom.h: patch_col, patch_slot_off) of a kernel whose fragment c covers output columns
+// (TW == 32: (c & 1) * 16, else 0) + fj
+template <int NC, int TW, int PSH>
+__device__ __forceinline__ void patch_col_table(int (&ct)[NC][3], int fj, int fq, bool hf) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int col = (TW == 32) ? (c & 1) * 16 + fj : fj;
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) ct[c][kx] = patch_slot_off<PSH>(patch_col(col, kx, hf), fq);
+    }
+}
+
+// descriptor -> address: the source of this lane's 16 bytes of 32-channel chunk kc of the concatenated NHWC operand (in0, C0 channels per pixel: the
+// first nc0 chunks; in1, C1: the others), or the zero page.  d = (source pixel index << 5) | (logical slot * 8 elements), -1 = zero page
+// (stream_geom.h: patch_desc).  The caller hands it to its LDS-DMA (glds16s / glds16s_aux) together with the piece's LDS address.
+__device__ __forceinline__ const void *patch_src(const uint16_t *in0, unsigned C0, const uint16_t *in1, unsigned C1, int nc0, int kc, const void *zero_page, int d) {
+    const bool first = kc < nc0;   // wave-uniform: the three selects are scalar
+    const uint16_t *src = first ? in0 : in1;
+    const unsigned cs = first ? C0 : C1;
+    const int chunk = first ? kc : kc - nc0;
+    // the per-lane arithmetic under a BRANCH, as every kernel compiled it when this was written out in each of them (as a select of two finished
+    // addresses the ConvGRU's kernel measured +1.4 % in the paired A/B: its load phase is what bounds it)
+    const void *p = zero_page;
+    if (d >= 0) p = src + ((unsigned)(d >> 5) * cs + (unsigned)(chunk * 32 + (d & 31)));
+    return p;
+}
+// ... of ONE operand (both halves the same, nc0 = 0: every select above folds away)
+__device__ __forceinline__ const void *patch_src(const uint16_t *src, unsigned cs, int kc, const void *zero_page, int d) {
+    return patch_src(src, cs, src, cs, 0, kc, zero_page, d);
+}

@@ -16,6 +16,8 @@
 //     L2 byte, 3x the gather kernel.
 // LDS: 4 x 8 KiB ring + 2 x 24 KiB patch buffers = 80 KiB -> two workgroups per CU (160 KiB).
 // LDS layouts as conv_halo.hip (conflict-free: patch slot ^ ((x>>1)&3), weights k-slot-major).
+// The bookkeeping every kernel form below shares -- XCD-major workgroup order, tile decode, patch DMA descriptors, column-offset tables, descriptor ->
+// source address, counted waits -- is defined ONCE: stream_geom.h (plain integer geometry, tested on the host) and conv_stream.h.
 #include "conv_stream.h"
 #include <cstdlib>
 #include <type_traits>
@@ -34,7 +36,7 @@
 #ifndef V2X_STREAM_PSWZ_BUILD
 #define V2X_STREAM_PSWZ_BUILD 1
 #endif
-#define PSWZ(pc) (((pc) >> V2X_STREAM_PSWZ_BUILD) & 3)
+constexpr int PSH = V2X_STREAM_PSWZ_BUILD;   // the swizzle shift of stream_geom.h: PSWZ(pc) = patch_swz<PSH>(pc) = (pc >> PSH) & 3
 // Variants of stream8g that were built, measured and REMOVED from this file in round 4 (HISTORY.md "Round 3 -- measured and rejected" holds the
 // numbers, the code is in the git history up to commit 7e0187e): the 32x32x16-MFMA form (M32: bit-identical, 9-20 % slower), weight fragments
 // read two blocks ahead (PF = 2: +2.8-3.7 %), s_setprio in the load / MFMA phase (LPRIO, PRIO: no effect), the prefetch point inside a block
@@ -46,11 +48,6 @@
 #ifndef V2X_STREAM_LSS_BUILD
 #define V2X_STREAM_LSS_BUILD 1
 #endif
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // ---- epilogue shared by the 4-wave and the 8-wave kernels -------------------------------------------
 // Chained epilogue with its second-GEMM operands staged in LDS (stage_chain): [w2 in fragment order (i2, ks, fq, fj) x 16 B |
@@ -332,7 +329,7 @@ __device__ __forceinline__ void stream_epilogue(const StreamArgs &a, f32x4_t (&a
 
 template <int BCO, int TH, int TW, int EPI, bool SPLITK = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_stream_kernel(const StreamArgs a) {
-    constexpr int PW = TW + 2, PH = TH + 2, PW0 = TW / 2 + 2, PH0 = TH / 2 + 2;
+    constexpr int PW = TW + 2, PH = TH + 2, PW0 = TW / 2 + 2;
     constexpr int TCO = BCO / 16;
     constexpr int W_PIECES = BCO / 16;        // 1 KiB pieces per weight slice (BCO rows x 64 B)
     constexpr int SLICE_BYTES = BCO * 64;
@@ -351,20 +348,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int fj = lane & 15, fq = lane >> 4;
     const int NW = (wave + 4 < W_PIECES) ? 2 : 1;     // weight DMAs this wave issues per step (wave-uniform)
 
-    // XCD-aware order (see conv_igemm.hip)
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, i = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
-    const int co_tile = bid % a.n_co_tiles;
-    const int px_tile = bid / a.n_co_tiles;
-    const int txy = a.tiles_x * a.tiles_y;
-    const int n = px_tile / txy;
-    const int trem = px_tile - n * txy;
-    const int ty = trem / a.tiles_x;
-    const int tx = trem - ty * a.tiles_x;
-    const int y0 = ty * TH, x0 = tx * TW;
+    const int bid = xcd_major_bid(blockIdx.x, gridDim.x);
+    int co_tile, n, y0, x0;
+    stream_tile_coords<TH, TW>(a.tiles_x, a.tiles_y, a.n_co_tiles, bid, co_tile, n, y0, x0);
 
     const int nc0 = a.C0 >> 5, nchunks = (a.C0 + a.C1) >> 5;
     // the chunk range of this workgroup: all of them, or (SPLITK) the blockIdx.y-th of a.ksplit contiguous ranges (the host makes sure
@@ -387,20 +373,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int t = 0; t < 6; ++t) {
         const int L = (wave + 4 * t) * 64 + lane;
-        const int pix = L >> 2, phys = L & 3;
-        {
-            const int pr = pix / PW, pc = pix - pr * PW;
-            const int y = y0 - 1 + pr, x = x0 - 1 + pc;
-            const bool ok = pix < PH * PW && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-            pd_full[t] = ok ? ((((n * a.H + y) * a.W + x) << 5) | ((phys ^ PSWZ(pc)) << 3)) : -1;
-        }
-        {
-            const int Hs = a.H >> 1, Ws = a.W >> 1;
-            const int pr = pix / PW0, pc = pix - pr * PW0;
-            const int y = (y0 >> 1) - 1 + pr, x = (x0 >> 1) - 1 + pc;
-            const bool ok = pix < PH0 * PW0 && (unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws;
-            pd_half[t] = ok ? ((((n * Hs + y) * Ws + x) << 5) | ((phys ^ PSWZ(pc)) << 3)) : -1;
-        }
+        pd_full[t] = patch_desc<TH, TW, PSH>(a.H, a.W, n, y0, x0, L, false);
+        pd_half[t] = patch_desc<TH, TW, PSH>(a.H, a.W, n, y0, x0, L, true);
     }
     // (b) byte offset inside a patch row of this lane's B fragment f for tap column kx (pixel slot + swizzled k-slot)
     int frow[4], ct_full[4][3], ct_half[4][3];
@@ -410,10 +384,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         frow[f] = (TW == 32) ? 2 * wave + (f >> 1) : 4 * wave + f;
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
-            const int pcf = col + kx;                    // full res: column col + kx
-            const int pch = ((col + kx - 1) >> 1) + 1;   // half res: floor((col + kx - 1) / 2) + 1
-            ct_full[f][kx] = ((pcf << 2) + (fq ^ PSWZ(pcf))) * 16;
-            ct_half[f][kx] = ((pch << 2) + (fq ^ PSWZ(pch))) * 16;
+            const int pcf = patch_col(col, kx, false), pch = patch_col(col, kx, true);
+            ct_full[f][kx] = patch_slot_off<PSH>(pcf, fq);
+            ct_half[f][kx] = patch_slot_off<PSH>(pch, fq);
         }
     }
 
@@ -432,10 +405,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         int d = hf ? pd_half[0] : pd_full[0];
 #pragma unroll
         for (int u = 1; u < 6; ++u) d = (t == u) ? (hf ? pd_half[u] : pd_full[u]) : d;
-        const uint16_t *src = first ? a.in0 : a.in1;
-        const unsigned cs = first ? (unsigned)a.C0 : (unsigned)a.C1;
-        const unsigned off = (unsigned)(d >> 5) * cs + (unsigned)((first ? kc : kc - nc0) * 32 + (d & 31));
-        glds16s(d >= 0 ? (const void *)(src + off) : zero_page, s_patch + buf * PATCH_BYTES + (wave + 4 * t) * 1024);
+        glds16s(patch_src(a.in0, a.C0, a.in1, a.C1, nc0, kc, zero_page, d), s_patch + buf * PATCH_BYTES + (wave + 4 * t) * 1024);
     };
     auto issue_dummy = [&]() { glds16s(zero_page, s_dummy); };
 
@@ -603,7 +573,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // runs once and the compiler drops everything that would have to live across the epilogue)
     constexpr bool PERSIST = (EPI != SEPI_CHAIN);
     constexpr int TH = 16, TW = 32;
-    constexpr int PW = TW + 2, PH = TH + 2, PW0 = TW / 2 + 2, PH0 = TH / 2 + 2;
+    constexpr int PW = TW + 2, PH = TH + 2, PW0 = TW / 2 + 2;
     constexpr int TCO = BCO / 16;
     constexpr int W_PIECES = BCO / 16;
     constexpr int SLICE_BYTES = BCO * 64;
@@ -626,11 +596,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int fj = lane & 15, fq = lane >> 4;
 
     const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, i = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
+    const int bid = xcd_major_bid(blockIdx.x, nwg);
     const int n_tiles = a.n_px_tiles * a.n_co_tiles;
     const int co_tile = bid % a.n_co_tiles;        // the same for every tile of this workgroup (nwg % n_co_tiles == 0)
     const int txy = a.tiles_x * a.tiles_y;
@@ -642,31 +608,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     char *s_chain = smem + RING * SLICE_BYTES + 2 * PATCH8_BYTES;
     if constexpr (EPI == SEPI_CHAIN) stage_chain<BCO, 512>(a, s_chain);
 
-    // tile coordinates
-    auto tile_coords = [&](int t, int &n, int &y0, int &x0) {
-        const int px_tile = t / a.n_co_tiles;
-        n = px_tile / txy;
-        const int trem = px_tile - n * txy;
-        const int ty = trem / a.tiles_x;
-        y0 = ty * TH;
-        x0 = (trem - ty * a.tiles_x) * TW;
-    };
-    // DMA source descriptor of patch piece (wave + 8t) for a tile at (n, y0, x0):
-    // (source pixel index << 5) | (swizzled 16-B slot * 8 elements), -1 = zero page
+    auto tile_coords = [&](int t, int &n, int &y0, int &x0) { stream_tile_coords<TH, TW>(a.tiles_x, a.n_co_tiles, txy, t, n, y0, x0); };
+    // DMA source descriptor of patch piece (wave + 8t) for a tile at (n, y0, x0)
     auto desc = [&](int n, int y0, int x0, int t, bool hf) -> int {
-        const int L = (wave + 8 * t) * 64 + lane;
-        const int pix = L >> 2, phys = L & 3;
-        if (!hf) {
-            const int pr = pix / PW, pc = pix - pr * PW;
-            const int y = y0 - 1 + pr, x = x0 - 1 + pc;
-            const bool ok = pix < PH * PW && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-            return ok ? ((((n * a.H + y) * a.W + x) << 5) | ((phys ^ PSWZ(pc)) << 3)) : -1;
-        }
-        const int Hs = a.H >> 1, Ws = a.W >> 1;
-        const int pr = pix / PW0, pc = pix - pr * PW0;
-        const int y = (y0 >> 1) - 1 + pr, x = (x0 >> 1) - 1 + pc;
-        const bool ok = pix < PH0 * PW0 && (unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws;
-        return ok ? ((((n * Hs + y) * Ws + x) << 5) | ((phys ^ PSWZ(pc)) << 3)) : -1;
+        return patch_desc<TH, TW, PSH>(a.H, a.W, n, y0, x0, (wave + 8 * t) * 64 + lane, hf);
     };
 
     // per-lane fragment tables.  ONE column-offset table, valid for the resolution of the chunk being computed (it is
@@ -675,17 +620,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     int frow[4], ct[4][3];
 #pragma unroll
     for (int f = 0; f < 4; ++f) frow[f] = 8 * grp + 2 * wv + (f >> 1);
-    auto build_ct = [&](bool hf) {
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const int col = (f & 1) * 16 + fj;
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int pc = hf ? (((col + kx - 1) >> 1) + 1) : (col + kx);
-                ct[f][kx] = ((pc << 2) + (fq ^ PSWZ(pc))) * 16;
-            }
-        }
-    };
 
     const bool has_w = wave < W_PIECES;                       // wave-uniform
     const uint16_t *wsrc = wbase + lane * 8 + wave * 512;
@@ -695,11 +629,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         else issue_dummy();
     };
     auto issue_piece = [&](int d, int kc, int t, int buf) {   // exactly one DMA; d = descriptor of this lane
-        const bool first = kc < nc0;
-        const uint16_t *src = first ? a.in0 : a.in1;
-        const unsigned cs = first ? (unsigned)a.C0 : (unsigned)a.C1;
-        const unsigned off = (unsigned)(d >> 5) * cs + (unsigned)((first ? kc : kc - nc0) * 32 + (d & 31));
-        glds16s(d >= 0 ? (const void *)(src + off) : zero_page, s_patch + buf * PATCH8_BYTES + (wave + 8 * t) * 1024);
+        glds16s(patch_src(a.in0, a.C0, a.in1, a.C1, nc0, kc, zero_page, d), s_patch + buf * PATCH8_BYTES + (wave + 8 * t) * 1024);
     };
     const bool chunk0_half = (nc0 > 0) && a.up0;
 
@@ -758,7 +688,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 }
                 pd_half = hfn;
             }
-            if (kc == 0 || kc == nc0) build_ct(half);  // wave-uniform
+            if (kc == 0 || kc == nc0) patch_col_table<4, TW, PSH>(ct, fj, fq, half);  // wave-uniform
 #pragma unroll 1
             for (int ky = 0; ky < 3; ++ky) {
                 int rowoff[4];
@@ -894,7 +824,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr int NF = WT ? 8 : 4;
     constexpr int NB = WT ? 12 : 8;                        // pixel fragments a wave reads per step
     constexpr int BT = (HCO % 2 == 0) ? 2 : HCO;           // WT: channel tiles per MFMA block (2 -> blocks of 16 MFMAs, 3 -> of 24)
-    constexpr int PSH = V2X_STREAM_PSWZ_BUILD;             // patch swizzle shift
     // output-store instructions per wave and tile (the counted waits after an epilogue leave exactly these in flight): 8-byte stores per
     // (16-channel tile, 16-pixel fragment)
     constexpr int N_ST = (EPI == SEPI_GRU) ? (TCO / 3) * 2 : TCO * 2;   // dwordx4 stores (stream_epilogue X4); on the dwordx2 path (unaligned rows) the counted wait is merely stricter
@@ -910,17 +839,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int fj = lane & 15, fq = lane >> 4;
 
     const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, i = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-        if (a.xcd_walk != 0 && a.n_co_tiles == 8 && r == 0 && q == 32) {
-            // an XCD's 32 workgroups of a round: 8 pixel tiles x 4 channel tiles (5.0 MB of patches + 3.5 MB of weights through its 4-MiB L2)
-            // instead of 4 x 8 (2.5 + 7.1 MB); the two XCDs of a pair share the 8 pixel tiles.  Measured on the ConvGRU: FETCH_SIZE 1.47 -> 1.24 GB
-            // per 320 maps, time -0.1 +- 0.1 %, bit-identical (tools/gru_xcd_walk_probe.sh)
-            const int x = bid >> 5, i = bid & 31;
-            bid = (((x >> 1) * 8 + (i >> 2)) << 3) + (x & 1) * 4 + (i & 3);
-        }
+    int bid = xcd_major_bid(blockIdx.x, nwg);
+    if (a.xcd_walk != 0 && a.n_co_tiles == 8 && (nwg & 7) == 0 && (nwg >> 3) == 32) {   // 256 workgroups
+        // an XCD's 32 workgroups of a round: 8 pixel tiles x 4 channel tiles (5.0 MB of patches + 3.5 MB of weights through its 4-MiB L2)
+        // instead of 4 x 8 (2.5 + 7.1 MB); the two XCDs of a pair share the 8 pixel tiles.  Measured on the ConvGRU: FETCH_SIZE 1.47 -> 1.24 GB
+        // per 320 maps, time -0.1 +- 0.1 %, bit-identical (tools/gru_xcd_walk_probe.sh)
+        const int x = bid >> 5, i = bid & 31;
+        bid = (((x >> 1) * 8 + (i >> 2)) << 3) + (x & 1) * 4 + (i & 3);
     }
     const int n_tiles = a.n_px_tiles * a.n_co_tiles;
     const int co_tile = bid % a.n_co_tiles;
@@ -930,42 +855,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const uint16_t *wbase = a.w + (size_t)co_tile * nchunks * 9 * (BCO * 32);
     const void *zero_page = a.w + (size_t)a.n_co_tiles * nchunks * 9 * (BCO * 32);
 
-    auto tile_coords = [&](int t, int &n, int &y0, int &x0) {
-        const int px_tile = t / a.n_co_tiles;
-        n = px_tile / txy;
-        const int trem = px_tile - n * txy;
-        const int ty = trem / a.tiles_x;
-        y0 = ty * TH;
-        x0 = (trem - ty * a.tiles_x) * TW;
-    };
-    // lane id from VOLATILE asm: values derived from it cannot be hoisted out of the tile / chunk / step loops (as lane constants
-    // they would be -- dozens of registers kept, and spilled, across the MFMA phases)
-    auto fresh_lane = [&]() -> int {
-        int l;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-        return l;
-    };
-    auto desc = [&](int n, int y0, int x0, int t, bool hf) -> int {   // DMA source descriptor of patch piece (wv + 4t) (group 0 fills the patch)
-        const int L = (wv + 4 * t) * 64 + fresh_lane();
-        const int pix = L >> 2, phys = L & 3;
-        if (!hf) {
-            const int pr = pix / PW, pc = pix - pr * PW;
-            const int y = y0 - 1 + pr, x = x0 - 1 + pc;
-            const bool ok = pix < PH * PW && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-            return ok ? ((((n * a.H + y) * a.W + x) << 5) | ((phys ^ ((pc >> PSH) & 3)) << 3)) : -1;
-        }
-        const int Hs = a.H >> 1, Ws = a.W >> 1;
-        const int pr = pix / PW0, pc = pix - pr * PW0;
-        const int y = (y0 >> 1) - 1 + pr, x = (x0 >> 1) - 1 + pc;
-        const bool ok = pix < PH0 * PW0 && (unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws;
-        return ok ? ((((n * Hs + y) * Ws + x) << 5) | ((phys ^ ((pc >> PSH) & 3)) << 3)) : -1;
+    auto tile_coords = [&](int t, int &n, int &y0, int &x0) { stream_tile_coords<TH, TW>(a.tiles_x, a.n_co_tiles, txy, t, n, y0, x0); };
+    // DMA source descriptor of patch piece (wv + 4t) (group 0 fills the patch), from fresh_lane(): the descriptors are rebuilt inside the loops
+    auto desc = [&](int n, int y0, int x0, int t, bool hf) -> int {
+        return patch_desc<TH, TW, PSH>(a.H, a.W, n, y0, x0, (wv + 4 * t) * 64 + fresh_lane(), hf);
     };
     auto issue_piece = [&](int d, int kc, int t, int buf) {
-        const bool first = kc < nc0;
-        const uint16_t *src = first ? a.in0 : a.in1;
-        const unsigned cs = first ? (unsigned)a.C0 : (unsigned)a.C1;
-        const unsigned off = (unsigned)(d >> 5) * cs + (unsigned)((first ? kc : kc - nc0) * 32 + (d & 31));
-        glds16s_aux<V2X_STREAM8G_PATCH_AUX>(d >= 0 ? (const void *)(src + off) : zero_page, s_patch + buf * PATCH8_BYTES + (wv + 4 * t) * 1024);
+        glds16s_aux<V2X_STREAM8G_PATCH_AUX>(patch_src(a.in0, a.C0, a.in1, a.C1, nc0, kc, zero_page, d), s_patch + buf * PATCH8_BYTES + (wv + 4 * t) * 1024);
     };
     // weight pieces of step `st` (chunk st / 3, tap column st % 3): piece p = wq + NQ * u, p < 3 * W_PIECES, for worker wq of NQ
     // (the prologue spreads a step over all 8 waves, the steady state over the 4 waves of group 1);
@@ -1272,19 +1168,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fj = lane & 15, fq = lane >> 4;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, i = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
-    const int co_tile = bid % a.n_co_tiles;
-    const int px_tile = bid / a.n_co_tiles;
-    const int txy = a.tiles_x * a.tiles_y;
-    const int n = px_tile / txy;
-    const int trem = px_tile - n * txy;
-    const int ty = trem / a.tiles_x;
-    const int tx = trem - ty * a.tiles_x;
-    const int y0 = ty * TH, x0 = tx * TW;
+    const int bid = xcd_major_bid(blockIdx.x, gridDim.x);
+    int co_tile, n, y0, x0;
+    stream_tile_coords<TH, TW>(a.tiles_x, a.tiles_y, a.n_co_tiles, bid, co_tile, n, y0, x0);
 
     const int nc0 = a.C0 >> 5, nchunks = (a.C0 + a.C1) >> 5;
     const int S = nchunks * 9;
@@ -1303,22 +1189,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         asm volatile("" : "+v"(lane_o));
 #pragma unroll
         for (int t = 0; t < PPW; ++t) {
-            const int L = (wave + 4 * t) * 64 + lane_o;
-            const int pix = L >> 2, phys = L & 3;
-            int d;
-            if (!hf) {
-                const int pr = pix / PW, pc = pix - pr * PW;
-                const int y = y0 - 1 + pr, x = x0 - 1 + pc;
-                const bool ok = pix < PH * PW && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-                d = ok ? ((((n * a.H + y) * a.W + x) << 5) | ((phys ^ PSWZ(pc)) << 3)) : -1;
-            } else {
-                const int Hs = a.H >> 1, Ws = a.W >> 1;
-                const int pr = pix / PW0, pc = pix - pr * PW0;
-                const int y = (y0 >> 1) - 1 + pr, x = (x0 >> 1) - 1 + pc;
-                const bool ok = pix < PH0 * PW0 && (unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws;
-                d = ok ? ((((n * Hs + y) * Ws + x) << 5) | ((phys ^ PSWZ(pc)) << 3)) : -1;
-            }
-            pd[t] = d;
+            pd[t] = patch_desc<TH, TW, PSH>(a.H, a.W, n, y0, x0, (wave + 4 * t) * 64 + lane_o, hf);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -1326,17 +1197,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     int frow[NF], ct[2][3];
 #pragma unroll
     for (int f = 0; f < NF; ++f) frow[f] = 4 * wave + (f >> 1);
-    auto build_ct = [&](bool hf) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int col = c * 16 + fj;
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int pc = hf ? (((col + kx - 1) >> 1) + 1) : (col + kx);
-                ct[c][kx] = ((pc << 2) + (fq ^ PSWZ(pc))) * 16;
-            }
-        }
-    };
 
     const uint16_t *wsrc = wbase + lane * 8 + wave * 512;
     auto issue_weights = [&](int s) {   // one DMA (BCO = 64: 4 pieces, one per wave)
@@ -1353,8 +1213,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             int d = pd[t];
             asm volatile("" : "+v"(d));   // keep the address arithmetic HERE: hoisted out of the chunk loop it becomes ten
                                           // live 64-bit addresses on top of 176 busy registers (it spilled)
-            const unsigned off = (unsigned)(d >> 5) * cs + (unsigned)((first ? kc : kc - nc0) * 32 + (d & 31));
-            glds16s(d >= 0 ? (const void *)(src + off) : zero_page, s_patch + (wave + 4 * t) * 1024);
+            glds16s(patch_src(src, cs, first ? kc : kc - nc0, zero_page, d), s_patch + (wave + 4 * t) * 1024);
         }
     };
 
@@ -1375,7 +1234,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int sh = half ? 1 : 0, row_bytes = (half ? PW0 : PW) * 64;
         if (kc == 0 || half != cur_half) {   // wave-uniform
             build_pd(half);
-            build_ct(half);
+            patch_col_table<2, TW, PSH>(ct, fj, fq, half);
             cur_half = half;
         }
         // ---- chunk boundary: everyone has left the previous chunk's patch (and ring slot s-1) -> refill, drain, meet
@@ -1428,7 +1287,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 template <int BCO>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_wide3_kernel(const StreamArgs a) {
     constexpr int TH = 16, TW = 32, NF = 8, NB = 12;
-    constexpr int PW = TW + 2, PH = TH + 2, PW0 = TW / 2 + 2, PH0 = TH / 2 + 2;
+    constexpr int PW = TW + 2, PW0 = TW / 2 + 2, PH0 = TH / 2 + 2;
     constexpr int TCO = BCO / 16;
     constexpr int SLICE_BYTES = BCO * 64, STEP_BYTES = 3 * SLICE_BYTES;
     constexpr int PPW = (WPATCH_PIECES + 3) / 4;   // patch pieces per wave (10)
@@ -1443,19 +1302,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fj = lane & 15, fq = lane >> 4;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, i = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
-    const int co_tile = bid % a.n_co_tiles;
-    const int px_tile = bid / a.n_co_tiles;
-    const int txy = a.tiles_x * a.tiles_y;
-    const int n = px_tile / txy;
-    const int trem = px_tile - n * txy;
-    const int ty = trem / a.tiles_x;
-    const int tx = trem - ty * a.tiles_x;
-    const int y0 = ty * TH, x0 = tx * TW;
+    const int bid = xcd_major_bid(blockIdx.x, gridDim.x);
+    int co_tile, n, y0, x0;
+    stream_tile_coords<TH, TW>(a.tiles_x, a.tiles_y, a.n_co_tiles, bid, co_tile, n, y0, x0);
 
     const int nc0 = a.C0 >> 5, nchunks = (a.C0 + a.C1) >> 5;
     const int S3 = nchunks * 3;
@@ -1468,39 +1317,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         asm volatile("" : "+v"(lane_o));
 #pragma unroll
         for (int t = 0; t < PPW; ++t) {
-            const int L = (wave + 4 * t) * 64 + lane_o;
-            const int pix = L >> 2, phys = L & 3;
-            int d;
-            if (!hf) {
-                const int pr = pix / PW, pc = pix - pr * PW;
-                const int y = y0 - 1 + pr, x = x0 - 1 + pc;
-                const bool ok = pix < PH * PW && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-                d = ok ? ((((n * a.H + y) * a.W + x) << 5) | ((phys ^ PSWZ(pc)) << 3)) : -1;
-            } else {
-                const int Hs = a.H >> 1, Ws = a.W >> 1;
-                const int pr = pix / PW0, pc = pix - pr * PW0;
-                const int y = (y0 >> 1) - 1 + pr, x = (x0 >> 1) - 1 + pc;
-                const bool ok = pix < PH0 * PW0 && (unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws;
-                d = ok ? ((((n * Hs + y) * Ws + x) << 5) | ((phys ^ PSWZ(pc)) << 3)) : -1;
-            }
-            pd[t] = d;
+            pd[t] = patch_desc<TH, TW, PSH>(a.H, a.W, n, y0, x0, (wave + 4 * t) * 64 + lane_o, hf);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
     int frow[NF], ct[2][3];
 #pragma unroll
     for (int f = 0; f < NF; ++f) frow[f] = 4 * wave + (f >> 1);
-    auto build_ct = [&](bool hf) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int col = c * 16 + fj;
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int pc = hf ? (((col + kx - 1) >> 1) + 1) : (col + kx);
-                ct[c][kx] = ((pc << 2) + (fq ^ PSWZ(pc))) * 16;
-            }
-        }
-    };
 
     const uint16_t *wsrc = wbase + lane * 8 + wave * 512;
     auto issue_weights = [&](int st) {   // step st = (chunk st / 3, tap column st % 3): this wave's piece of each of the three tap slices
@@ -1520,8 +1343,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if (wave + 4 * t >= npieces) break;              // wave-uniform
             int d = pd[t];
             asm volatile("" : "+v"(d));
-            const unsigned off = (unsigned)(d >> 5) * cs + (unsigned)((first ? kc : kc - nc0) * 32 + (d & 31));
-            glds16s(d >= 0 ? (const void *)(src + off) : zero_page, s_patch + (wave + 4 * t) * 1024);
+            glds16s(patch_src(src, cs, first ? kc : kc - nc0, zero_page, d), s_patch + (wave + 4 * t) * 1024);
         }
     };
 
@@ -1541,7 +1363,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int sh = half ? 1 : 0, row_bytes = (half ? PW0 : PW) * 64;
         if (kc == 0 || half != cur_half) {   // wave-uniform
             build_pd(half);
-            build_ct(half);
+            patch_col_table<2, TW, PSH>(ct, fj, fq, half);
             cur_half = half;
         }
         // ---- chunk boundary: everyone has left the previous chunk's patch -> refill, drain (also the weights in flight), meet

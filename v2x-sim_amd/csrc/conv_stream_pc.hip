@@ -31,7 +31,7 @@
 // Weight layout (w_layout 4, v2x_pack_conv / packing.pack_conv_stream_parity): per 128-row channel tile
 //   [C0 / 32 chunks][4 class taps 2 a + b][4 classes 2 py + px][4 k-slots][128 rows][8]   then   [C1 / 32 chunks][kx][ky][4 k-slots][128 rows][8],
 // followed (after the last tile) by 64 B of zeros, the zero page.
-#include "conv_stream.h"
+#include "conv_stream.h"   // remap, tile decode, the up phase's half-resolution patch descriptor and its DMA source: the shared definitions (stream_geom.h)
 
 namespace pcs {
 constexpr int TH = 16, TW = 32, BCO = 128, TCO = 8, HCO = 4;
@@ -53,7 +53,7 @@ constexpr int OFF_UPA = NU * USTEP, OFF_UPB = OFF_UPA + UP_PIECES * 1024;
 constexpr int OFF_SS = (OFF_UPB + UP_PIECES * 1024 > OFF_P1 + SP_PIECES * 1024) ? OFF_UPB + UP_PIECES * 1024 : OFF_P1 + SP_PIECES * 1024;
 constexpr int SMEM = OFF_SS + 2 * BCO * 4;
 static_assert(SMEM <= 160 * 1024 && (NU == 3 || NU == 4), "LDS map");
-#define PCS_SWZ(pc) (((pc) >> 1) & 3)
+constexpr int PSH = 1;                                 // patch swizzle shift (stream_geom.h: patch_swz), both patch forms
 
 }  // namespace pcs
 
@@ -68,11 +68,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int fj = lane & 15, fq = lane >> 4;
 
     const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, i = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
+    const int bid = xcd_major_bid(blockIdx.x, nwg);
     const int n_tiles = a.n_px_tiles * a.n_co_tiles;
     const int co_tile = bid % a.n_co_tiles;
     const int txy = a.tiles_x * a.tiles_y;
@@ -82,31 +78,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const char *w_up = reinterpret_cast<const char *>(a.w) + (size_t)co_tile * tile_bytes;
     const char *w_sk = w_up + (size_t)S_up * USTEP;
     const void *zero_page = reinterpret_cast<const char *>(a.w) + (size_t)a.n_co_tiles * tile_bytes;
-    const int Hs = a.H >> 1, Ws = a.W >> 1;
 
-    auto tile_coords = [&](int t, int &n, int &y0, int &x0) {
-        const int px_tile = t / a.n_co_tiles;
-        n = px_tile / txy;
-        const int trem = px_tile - n * txy;
-        const int ty = trem / a.tiles_x;
-        y0 = ty * TH;
-        x0 = (trem - ty * a.tiles_x) * TW;
-    };
-    // lane id from volatile asm: what is derived from it is recomputed where it is used instead of living in registers across the MFMA phases
-    auto fresh_lane = [&]() -> int {
-        int l;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-        return l;
-    };
+    auto tile_coords = [&](int t, int &n, int &y0, int &x0) { stream_tile_coords<TH, TW>(a.tiles_x, a.n_co_tiles, txy, t, n, y0, x0); };
     // ---- LDS-DMA issue helpers (one instruction = one 1-KiB piece) ------------------------------------------------------------------------
     auto issue_up_patch_piece = [&](int n, int y0, int x0, int kc, int piece, int buf_off) {   // half-resolution patch of up chunk kc
-        const int L = piece * 64 + fresh_lane();
-        const int pix = L >> 2, phys = L & 3;
-        const int pr = pix / PW0, pc = pix - pr * PW0;
-        const int y = (y0 >> 1) - 1 + pr, x = (x0 >> 1) - 1 + pc;
-        const bool ok = pix < PH0 * PW0 && (unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws;
-        const unsigned off = (unsigned)((n * Hs + y) * Ws + x) * (unsigned)a.C0 + (unsigned)(kc * 32 + ((phys ^ PCS_SWZ(pc)) << 3));
-        glds16s(ok ? (const void *)(a.in0 + off) : zero_page, smem + buf_off + piece * 1024);
+        const int d = patch_desc<pcs::TH, pcs::TW, pcs::PSH>(a.H, a.W, n, y0, x0, piece * 64 + fresh_lane(), true);
+        glds16s(patch_src(a.in0, (unsigned)a.C0, kc, zero_page, d), smem + buf_off + piece * 1024);
     };
     auto issue_sk_patch_piece = [&](int n, int y0, int x0, int kc, int piece, int buf_off) {   // full-resolution patch of skip chunk kc, two parity planes
         const int L = piece * 64 + fresh_lane();
@@ -115,7 +92,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int pr = rem / PWH, cc = rem - pr * PWH;
         const int y = y0 - 1 + pr, x = x0 - 1 + 2 * cc + q;
         const bool ok = pix < 2 * PHF * PWH && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-        const unsigned off = (unsigned)((n * a.H + y) * a.W + x) * (unsigned)a.C1 + (unsigned)(kc * 32 + ((phys ^ PCS_SWZ(cc)) << 3));
+        const unsigned off = (unsigned)((n * a.H + y) * a.W + x) * (unsigned)a.C1 + (unsigned)(kc * 32 + ((phys ^ patch_swz<pcs::PSH>(cc)) << 3));
         glds16s(ok ? (const void *)(a.in1 + off) : zero_page, smem + buf_off + piece * 1024);
     };
     auto issue_up_weights = [&](int st, int first, int count) {   // pieces [first, first + count) of up step st's 32-KiB slot image
@@ -198,7 +175,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 bf16x8_t B[4], A[TCO];
                 {
                     const int pc = fjl + tb + px;
-                    const char *p = pb + ((4 * grp + py + ta) * PW0 * 4 + pc * 4 + (fql ^ PCS_SWZ(pc))) * 16;
+                    const char *p = pb + ((4 * grp + py + ta) * PW0 * 4 + pc * 4 + (fql ^ patch_swz<pcs::PSH>(pc))) * 16;
 #pragma unroll
                     for (int y = 0; y < 4; ++y) B[y] = *reinterpret_cast<const bf16x8_t *>(p + y * (PW0 * 64));
                     const char *ws = smem + (st % NU) * USTEP + wv * SLICE + (fql * BCO + fjl) * 16;
@@ -273,7 +250,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const char *ws = smem + (st % 3) * SSTEP + (fql * BCO + fjl) * 16;
                 {
                     const int q = (px + kx) & 1, cc = fjl + ((px + kx) >> 1);
-                    const char *p = pb + (((q * PHF + 8 * grp + py) * PWH + cc) * 4 + (fql ^ PCS_SWZ(cc))) * 16;
+                    const char *p = pb + (((q * PHF + 8 * grp + py) * PWH + cc) * 4 + (fql ^ patch_swz<pcs::PSH>(cc))) * 16;
 #pragma unroll
                     for (int r = 0; r < 9; ++r) B[r] = *reinterpret_cast<const bf16x8_t *>(p + r * (PWH * 64));
 #pragma unroll
@@ -392,11 +369,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int py = wv >> 1, px = wv & 1;
     const int fj = lane & 15, fq = lane >> 4;
     const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, i = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
+    const int bid = xcd_major_bid(blockIdx.x, nwg);
     const int n_tiles = a.n_px_tiles;                 // 16 x 64 regions; one channel tile
     const int txy = a.tiles_x * a.tiles_y;
     const int n_up = a.C0 >> 5, n_sk = a.C1 >> 5;
@@ -404,28 +377,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const char *w_up = reinterpret_cast<const char *>(a.w);
     const char *w_sk = w_up + (size_t)S_up * USTEP;
     const void *zero_page = w_sk + (size_t)S_sk * SSTEP;
-    const int Hs = a.H >> 1, Ws = a.W >> 1;
 
-    auto tile_coords = [&](int t, int &n, int &y0, int &x0) {   // x0 = this GROUP's tile
-        n = t / txy;
-        const int trem = t - n * txy;
-        const int ty = trem / a.tiles_x;
-        y0 = ty * TH;
-        x0 = (trem - ty * a.tiles_x) * 64 + 32 * grp;
-    };
-    auto fresh_lane = [&]() -> int {
-        int l;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-        return l;
+    auto tile_coords = [&](int t, int &n, int &y0, int &x0) {   // 16 x 64 regions; x0 = this GROUP's tile
+        px_tile_coords<TH, 64>(a.tiles_x, txy, t, n, y0, x0);
+        x0 += 32 * grp;
     };
     auto issue_up_patch_piece = [&](int n, int y0, int x0, int kc, int piece, int buf_off) {
-        const int L = piece * 64 + fresh_lane();
-        const int pix = L >> 2, phys = L & 3;
-        const int pr = pix / PW0, pc = pix - pr * PW0;
-        const int y = (y0 >> 1) - 1 + pr, x = (x0 >> 1) - 1 + pc;
-        const bool ok = pix < PH0 * PW0 && (unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws;
-        const unsigned off = (unsigned)((n * Hs + y) * Ws + x) * (unsigned)a.C0 + (unsigned)(kc * 32 + ((phys ^ PCS_SWZ(pc)) << 3));
-        glds16s(ok ? (const void *)(a.in0 + off) : zero_page, smem + buf_off + piece * 1024);
+        const int d = patch_desc<pcs::TH, pcs::TW, pcs::PSH>(a.H, a.W, n, y0, x0, piece * 64 + fresh_lane(), true);
+        glds16s(patch_src(a.in0, (unsigned)a.C0, kc, zero_page, d), smem + buf_off + piece * 1024);
     };
     auto issue_sk_patch_piece = [&](int n, int y0, int x0, int kc, int piece, int buf_off) {
         const int L = piece * 64 + fresh_lane();
@@ -434,7 +393,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int pr = rem / PWH, cc = rem - pr * PWH;
         const int y = y0 - 1 + pr, x = x0 - 1 + 2 * cc + q;
         const bool ok = pix < 2 * PHF * PWH && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-        const unsigned off = (unsigned)((n * a.H + y) * a.W + x) * (unsigned)a.C1 + (unsigned)(kc * 32 + ((phys ^ PCS_SWZ(cc)) << 3));
+        const unsigned off = (unsigned)((n * a.H + y) * a.W + x) * (unsigned)a.C1 + (unsigned)(kc * 32 + ((phys ^ patch_swz<pcs::PSH>(cc)) << 3));
         glds16s(ok ? (const void *)(a.in1 + off) : zero_page, smem + buf_off + piece * 1024);
     };
     auto issue_up_weights = [&](int st, int first, int count) {
@@ -508,7 +467,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 bf16x8_t B[8], A[TCO];
                 {
                     const int pc = fjl + tb + px;
-                    const char *p = pb + ((py + ta) * PW0 * 4 + pc * 4 + (fql ^ PCS_SWZ(pc))) * 16;
+                    const char *p = pb + ((py + ta) * PW0 * 4 + pc * 4 + (fql ^ patch_swz<pcs::PSH>(pc))) * 16;
 #pragma unroll
                     for (int y = 0; y < 8; ++y) B[y] = *reinterpret_cast<const bf16x8_t *>(p + y * (PW0 * 64));
                     const char *ws = smem + (st % 3) * USTEP + wv * SLICE + (fql * BCO + fjl) * 16;
@@ -577,7 +536,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 bf16x8_t B[9], A[3][TCO];
                 const char *ws = smem + (st % 3) * SSTEP + (fql * BCO + fjl) * 16;
                 const int q = (px + kx) & 1, cc = fjl + ((px + kx) >> 1);
-                const char *p = pb + (((q * PHF + py) * PWH + cc) * 4 + (fql ^ PCS_SWZ(cc))) * 16;
+                const char *p = pb + (((q * PHF + py) * PWH + cc) * 4 + (fql ^ patch_swz<pcs::PSH>(cc))) * 16;
 #pragma unroll
                 for (int r = 0; r < 9; ++r) B[r] = *reinterpret_cast<const bf16x8_t *>(p + r * (PWH * 64));
 #pragma unroll

@@ -14,7 +14,7 @@
 //     the one of conv_stream.hip (packing.pack_conv_stream), so a layer is packed the same way for either stride.
 // One patch buffer (37 KiB) + ring (16 / 32 KiB) = 53 / 69 KiB -> three / two workgroups per CU; the patch refill at a
 // chunk boundary (everything drains there) is what the other workgroups cover.
-#include "common.h"
+#include "conv_stream.h"   // shared with the stride-1 kernels: workgroup remap, tile decode, descriptor -> address, LDS-DMA, counted waits
 #ifndef V2X_S2_PSWZ_BUILD
 #define V2X_S2_PSWZ_BUILD 1   // patch swizzle (entry >> 1) & 3; 2 = (entry >> 2) & 3 (conv_stream.hip PSWZ): measured no different here (297 vs 299 us)
 #endif
@@ -23,7 +23,6 @@
 #endif
 #include <cstdlib>
 
-int v2x_num_cus();   // conv_stream.hip
 #if (V2X_S2G_DBG_BUILD & 64)
 // timestamp build (tools/s2g_timeline.sh): lane 0 of wave 0 of each group of workgroup 0 stamps the shader clock at 6 points of each of its
 // first S2G_T_STEPS steps: 0 top of the load phase, 1 DMAs issued, 2 fragments read + waits done, 3 first barrier passed, 4 MFMAs done, 5 end-of-phase wait done
@@ -33,13 +32,6 @@ extern "C" int v2x_debug_s2g_timeline(unsigned *dst) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(v2x_s2g_timeline), sizeof(unsigned) * 2 * S2G_T_STEPS * 8);
 }
 #endif
-
-typedef const __attribute__((address_space(1))) void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
-
-__device__ __forceinline__ void glds16q(const void *g, char *lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
 
 struct S2Args {
     const uint16_t *in;   // [N][H][W][C] bf16
@@ -84,11 +76,6 @@ struct S2Geom {
     static_assert(PIECES * 1024 <= S2_PATCH_BYTES, "patch must fit the common buffer");
 };
 
-template <int N>
-__device__ __forceinline__ void s2_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int BCO, int TH = S2_TH, int TW = S2_TW, bool SPLITK = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) void conv3x3_s2_stream_kernel(const S2Args a) {
     using G = S2Geom<TH, TW>;
@@ -108,19 +95,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fj = lane & 15, fq = lane >> 4;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, i = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
-    const int co_tile = bid % a.n_co_tiles;
-    const int px_tile = bid / a.n_co_tiles;
-    const int txy = a.tiles_x * a.tiles_y;
-    const int n = px_tile / txy;
-    const int trem = px_tile - n * txy;
-    const int ty = trem / a.tiles_x;
-    const int tx = trem - ty * a.tiles_x;
-    const int y0 = ty * TH, x0 = tx * TW;       // output coordinates
+    const int bid = xcd_major_bid(blockIdx.x, gridDim.x);
+    int co_tile, n, y0, x0;                     // output coordinates
+    stream_tile_coords<TH, TW>(a.tiles_x, a.tiles_y, a.n_co_tiles, bid, co_tile, n, y0, x0);
 
     const int nchunks = a.C >> 5;
     // SPLITK: this workgroup walks the chunks [kc_lo, kc_hi) of the layer's K (blockIdx.y = its range)
@@ -170,16 +147,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
     auto issue_weights = [&](int s) {   // NW DMAs
         char *dst = s_ring + (s & (S2_RING - 1)) * SLICE_BYTES;
         const uint16_t *src = wsrc + (size_t)s * (BCO * 32);
-        glds16q(src, dst + wave * 1024);
-        if (NW == 2) glds16q(src + 4 * 512, dst + (wave + 4) * 1024);
+        glds16s(src, dst + wave * 1024);
+        if (NW == 2) glds16s(src + 4 * 512, dst + (wave + 4) * 1024);
     };
     auto issue_patch = [&](int kc) {    // this wave's pieces of chunk kc (pieces >= S2_PIECES do not exist)
 #pragma unroll
         for (int t = 0; t < G::PPW; ++t) {
             if (wave + 4 * t >= G::PIECES) break;            // wave-uniform
-            const int d = pd[t];
-            const unsigned off = (unsigned)(d >> 5) * (unsigned)a.C + (unsigned)(kc * 32 + (d & 31));
-            glds16q(d >= 0 ? (const void *)(a.in + off) : zero_page, s_patch + (wave + 4 * t) * 1024);
+            glds16s(patch_src(a.in, (unsigned)a.C, kc, zero_page, pd[t]), s_patch + (wave + 4 * t) * 1024);
         }
     };
 
@@ -199,7 +174,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
         // ---- chunk boundary: everyone has left the previous chunk's patch (and ring slot s-1) -> refill, drain, meet
         if (kc > kc_lo) __builtin_amdgcn_s_barrier();
         issue_patch(kc);
-        s2_wait_vmcnt<0>();
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
 #pragma unroll 1
         for (int ky = 0; ky < 3; ++ky) {
@@ -209,8 +184,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
                 const int tap = ky * 3 + kx;
                 if (tap > 0) {
                     // this step's slice has landed (groups s+1, s+2 may be in flight); everyone is done with slot s-1
-                    if (s + 2 >= S) s2_wait_vmcnt<0>();
-                    else s2_wait_vmcnt<2 * NW>();
+                    if (s + 2 >= S) wait_vmcnt<0>();
+                    else wait_vmcnt<2 * NW>();
                     __builtin_amdgcn_s_barrier();
                 }
                 if (s + 3 < S) issue_weights(s + 3);
@@ -325,7 +300,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     // weights of the (single) channel tile: one linear LDS-DMA copy
     for (int off = wave * 1024; off < W_BYTES; off += 4096)
-        glds16q(reinterpret_cast<const char *>(a.w) + off + lane * 16, s_w + off);
+        glds16s(reinterpret_cast<const char *>(a.w) + off + lane * 16, s_w + off);
 
     int ct[2][3];
 #pragma unroll
@@ -353,10 +328,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     bool first = true;
     const v2x_tile_walk walk = v2x_xcd_tile_walk(a.n_px_tiles, a.xcd_walk);     // neighbouring tiles (shared halo rows / columns) on one XCD: common.h
     for (int tile = walk.first; tile < walk.end; tile += walk.step) {
-        const int n = tile / txy;
-        const int trem = tile - n * txy;
-        const int ty = trem / a.tiles_x;
-        const int y0 = ty * S2_TH, x0 = (trem - ty * a.tiles_x) * S2_TW;
+        int n, y0, x0;
+        px_tile_coords<S2_TH, S2_TW>(a.tiles_x, txy, tile, n, y0, x0);
         // everyone has left the patch of the previous tile (its MFMAs consumed their fragments)
         if (!first) __builtin_amdgcn_s_barrier();
 #pragma unroll
@@ -366,9 +339,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int y = 2 * y0 - 1 + (d >> 20), x = 2 * x0 - 1 + ((d >> 8) & 0xfff);
             const bool ok = d >= 0 && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
             const unsigned off = ((unsigned)(n * a.H + y) * (unsigned)a.W + (unsigned)x) * (unsigned)a.C + (unsigned)(d & 0xff);
-            glds16q(ok ? (const void *)(a.in + off) : zero_page, s_patch + (wave + 4 * t) * 1024);
+            glds16s(ok ? (const void *)(a.in + off) : zero_page, s_patch + (wave + 4 * t) * 1024);
         }
-        s2_wait_vmcnt<0>();     // the patch (and, the first time, the weights; later also the previous tile's stores)
+        wait_vmcnt<0>();     // the patch (and, the first time, the weights; later also the previous tile's stores)
         __builtin_amdgcn_s_barrier();
         first = false;
 
@@ -505,11 +478,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int R0 = grp * (TH / 2) + ph * G::RW;            // the wave's first output row of the tile
 
     const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, i = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
+    const int bid = xcd_major_bid(blockIdx.x, nwg);
     const int n_tiles = a.n_px_tiles * a.n_co_tiles;
     const int co_tile = bid % a.n_co_tiles;
     const int txy = a.tiles_x * a.tiles_y;
@@ -518,20 +487,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const uint16_t *wbase = a.w + (size_t)co_tile * nchunks * 9 * (BCO * 32);
     const void *zero_page = a.w + (size_t)a.n_co_tiles * nchunks * 9 * (BCO * 32);
 
-    auto tile_coords = [&](int t, int &n, int &y0, int &x0) {
-        const int px_tile = t / a.n_co_tiles;
-        n = px_tile / txy;
-        const int trem = px_tile - n * txy;
-        const int ty = trem / a.tiles_x;
-        y0 = ty * TH;
-        x0 = (trem - ty * a.tiles_x) * TW;
-    };
-    // lane id from volatile asm: what is derived from it is not hoisted out of the loops and kept in registers across the MFMA phases
-    auto fresh_lane = [&]() -> int {
-        int l;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-        return l;
-    };
+    auto tile_coords = [&](int t, int &n, int &y0, int &x0) { stream_tile_coords<TH, TW>(a.tiles_x, a.n_co_tiles, txy, t, n, y0, x0); };
     // tile-independent part of the DMA source descriptor of piece p of a patch region: (patch row << 16) | (patch column << 4) | logical
     // 16-B slot, -1 behind the region
     auto desc_const = [&](bool odd, int p, int lane) -> int {
@@ -549,8 +505,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
     auto issue_piece = [&](int d, int kc, char *dst) {
         if constexpr ((DBG & 2) != 0) return;
-        const unsigned off = (unsigned)(d >> 5) * (unsigned)a.C + (unsigned)(kc * 32 + (d & 31));
-        glds16q(d >= 0 ? (const void *)(a.in + off) : zero_page, dst);
+        glds16s(patch_src(a.in, (unsigned)a.C, kc, zero_page, d), dst);
     };
     // piece p = wv + 4u of step t (chunk t / 3, tap column j = t % 3 -> kx = 0, 2, 1); piece p = (tap row p / 8, piece p % 8 of its slice):
     // a wave's first two pieces (u = 0, 1) are tap row 0
@@ -560,7 +515,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int kx = j == 0 ? 0 : (j == 1 ? 2 : 1);
         const int p = wv + 4 * u;
         const int ky = p >> 3, pis = p & 7;
-        glds16q(wbase + (size_t)(kc * 9 + ky * 3 + kx) * (BCO * 32) + pis * 512 + lw * 8, s_ring + slot * STEP_BYTES + ky * SLICE_BYTES + pis * 1024);
+        glds16s(wbase + (size_t)(kc * 9 + ky * 3 + kx) * (BCO * 32) + pis * 512 + lw * 8, s_ring + slot * STEP_BYTES + ky * SLICE_BYTES + pis * 1024);
     };
     // s_waitcnt vmcnt(K) for the wave-uniform run-time K in {0, 4, 6, 8, 9} (+ N_ST)
     auto wait_keep = [&](int k, bool plus_stores) {

@@ -151,11 +151,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         ty = r / a.tiles_x;
         tx = r - ty * a.tiles_x;
     };
-    auto fresh_lane = [&]() -> int {   // recomputed where it is used: lane-derived DMA addresses hoisted out of the tile loop cost ~30 registers (spills)
-        int l;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-        return l;
-    };
+    // (fresh_lane(), conv_stream.h: recomputed where it is used -- lane-derived DMA addresses hoisted out of the tile loop cost ~30 registers (spills))
     // window fill: the lane's element offset from the window's first pixel per piece (tile-invariant: 7 registers); a tile away from the image border
     // (70 % of them at 256 x 256) needs no bounds test -- 3 VALU instructions per piece instead of ~15
     unsigned woff[PPW];
@@ -406,7 +402,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (grp == 0) __builtin_amdgcn_s_barrier();   // balance group 1's offset barrier
 }
 
-int v2x_num_cus();   // conv_stream.hip
 
 static int tail_launch(const TailArgs &a, hipStream_t s) {
     const int n_pairs = (a.n_tiles + 1) / 2;
