@@ -573,6 +573,26 @@ int v2x_det_nms_candidates(const unsigned long long *keys, const float *codes, c
                            int M, int cap, float nms_thr, int rotated, float *out_boxes, float *out_scores, int32_t *out_index,
                            int32_t *out_count, v2x_stream_t stream);
 
+/* Late fusion (upstream test_codet.py --com late, the paper's "Co-lower-bound"): the agents exchange their DETECTIONS; every ego moves its
+ * neighbours' boxes into its own frame and suppresses the union.  One workgroup per ego, all A*B egos of the call, at most two launches
+ * (as the NMS above: the second takes the egos with more than 512 merged candidates); no allocation, no host synchronisation.
+ * boxes fp32 [A*B][cap_in][5], scores fp32 [A*B][cap_in], counts int32 [A*B]: what v2x_det_postprocess / v2x_det_nms_candidates wrote, rows
+ *   agent-major (row of agent j in frame b = j*B + b).  A count above cap_in reads as cap_in.
+ * rigid fp32 [B][A][A][8]: entry (b, i, j) = (r00, r01, tx, r10, r11, ty, dyaw, 0) moves a box of agent j into ego i's frame:
+ *   x' = (r00*x + r01*y) + tx, y' = (r10*x + r11*y) + ty, yaw' = yaw + dyaw in fp32, every product and sum rounded on its own; w, h stay.
+ *   (From the dataset's trans_matrices: r = T[0:2, 0:2], tx = T13, ty = -T03, dyaw = atan2(T10, T00): utils/postprocess.late_rigid_from_trans.)
+ * link uint8 [B][A][A]: ego i of frame b receives from j; the diagonal says whether i itself is present (0: out_count 0).
+ * The ego's own detections enter bit for bit and uncropped; a neighbour's enter iff x_lo <= x' < x_hi and y_lo <= y' < y_hi.  A candidate with a
+ * non-finite field (score included) or a score that is not >= 0 is dropped.  Order: score descending; ties: the ego's own boxes, then neighbours by
+ * ascending agent index, then by ascending rank in the source list.  Suppression: exactly v2x_det_postprocess's (rotated != 0: _rotated's).
+ * out_boxes fp32 [A*B][cap_out][5], out_scores fp32 [A*B][cap_out] (the source's bits), out_src int32 [A*B][cap_out] = j*cap_in + rank of the
+ * source, out_count int32 [A*B]; negative = not computed: -(merged candidates) when they exceed cap_out, -(cap_out + 1) when the ego or a
+ * linked source carried a negative count itself.  cap_in, cap_out: powers of two in [64, 4096].  A*B == 0: nothing to do (V2X_OK). */
+int v2x_det_late_fuse(const float *boxes, const float *scores, const int32_t *counts, int A, int B, int cap_in,
+                      const float *rigid, const uint8_t *link, float x_lo, float x_hi, float y_lo, float y_hi,
+                      float nms_thr, int rotated, int cap_out, float *out_boxes, float *out_scores,
+                      int32_t *out_src, int32_t *out_count, v2x_stream_t stream);
+
 /* ---------------------------------------------------------------- f-1: the metric (coperception/utils/mean_ap.py::eval_map)
  * Upstream intersects shapely polygons on the host; here the IoU of rotated boxes (x, y, w, h, yaw) is a convex clip in
  * fp64 on the device.

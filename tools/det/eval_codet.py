@@ -4,7 +4,13 @@
     python tools/det/eval_codet.py --data /path/V2X-Sim-det/test --com mean --resume ckpt.pth --compress_level 2 --only_v2i 1
 
 --compress_level k (0..8) and --only_v2i 0|1 reach the model's constructor and are checked against the record tools/det/train_codet.py
-keeps in its checkpoints; every other flag is test_codet.py's own (v2x_sim_amd/utils/comm.py::run_eval_driver)."""
+keeps in its checkpoints; every other flag is test_codet.py's own (v2x_sim_amd/utils/comm.py::run_eval_driver).
+
+    python tools/det/eval_codet.py --data /path/V2X-Sim-det/test --com late --resume lowerbound.pth [--only_v2i 1]
+
+--com late is upstream's late fusion (the table's "Co-lower-bound"): test_codet.py runs as --com lowerbound, the FaFModule it builds exchanges the
+agents' detections and suppresses the union per ego (FaFModule.late_fusion; --only_v2i masks the links), and the share of the kept boxes that
+came from neighbours is printed after the scores."""
 import os
 import sys
 

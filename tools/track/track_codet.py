@@ -31,7 +31,7 @@ def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("-d", "--data", required=True, type=str, help="the {split} directory holding agent{k}/")
     ap.add_argument("--out", required=True, type=str, help="directory for the MOT-challenge text files")
-    ap.add_argument("--com", default="v2v", choices=["lowerbound", "upperbound", "v2v", "when2com", "who2com", "sum", "mean", "max", "cat", "disco"])
+    ap.add_argument("--com", default="v2v", choices=["lowerbound", "upperbound", "v2v", "when2com", "who2com", "sum", "mean", "max", "cat", "disco", "late"])
     ap.add_argument("--resume", default="", type=str, help="checkpoint with 'model_state_dict' (or a bare state_dict)")
     ap.add_argument("--num_agent", default=5, type=int)
     ap.add_argument("--rsu", default=1, type=int, help="1: agent0 (the RSU) takes part, 0: vehicles only")
@@ -66,7 +66,7 @@ def main(argv=None):
     roots = [os.path.join(args.data, "agent%d" % k) for k in range(first, first + args.num_agent)]
     dataset = V2XSimDet(dataset_roots=roots, config=config, config_global=config_global, split="test", val=True)
     A = args.num_agent
-    if args.com in ("lowerbound", "upperbound"):
+    if args.com in ("lowerbound", "upperbound", "late"):       # late: the lowerbound detector, boxes exchanged afterwards
         model = FaFNet(config, layer=args.layer, kd_flag=0, num_agent=A)
     elif args.com == "v2v":
         model = V2VNet(config, gnn_iter_times=args.gnn_iter_times, layer=args.layer, layer_channel=256, num_agent=A)
@@ -85,6 +85,8 @@ def main(argv=None):
     model = model.to(device)
     module = FaFModule(model, None, config, None, 0)
     module.score_thr = args.score_thr
+    if args.com == "late":
+        module.late_fusion = True
     inference = args.inference or ("argmax_test" if args.com == "who2com" else "activated")
 
     # the samples of every scene, in frame order ({scene}_{frame} names, already sorted numerically by the dataset)
@@ -140,6 +142,9 @@ def main(argv=None):
     if truncated:
         print("%d maps had more than %d detections: the tracker read the %d best" % (truncated, DET_CAP, DET_CAP))
     print("%d scenes x %d agents -> %d files, %d track lines under %s" % (len(order), A, len(written), n_lines, args.out))
+    if args.com == "late":
+        from v2x_sim_amd.utils import comm
+        print(comm.late_report(module.late_stats))
     return {"files": written, "lines": n_lines}
 
 

@@ -17,86 +17,7 @@
 //      of the sorted candidates into LDS, then the greedy scan -- candidate i is tested against the kept list by all
 //      threads in parallel (__syncthreads_or), so the serial depth is the number of candidates, not candidates x kept.
 #include "common.h"
-
-constexpr int DET_MAX_CAP = 4096;
-
-// ---- rotated-box IoU (row f-1: upstream's eval_map intersects shapely polygons; here: convex clipping in fp64) ----------
-// Corners of (x, y, w, h, yaw), counter-clockwise, first = (+w/2, +h/2) rotated (the order of utils/postprocess.box_corners).
-__device__ __forceinline__ void box_corners_d(const float *b, double (&cx)[4], double (&cy)[4]) {
-    const double x = b[0], y = b[1], w = b[2], h = b[3], yaw = b[4];
-    const double c = cos(yaw), s = sin(yaw);
-    const double dx[4] = {0.5 * w, -0.5 * w, -0.5 * w, 0.5 * w}, dy[4] = {0.5 * h, 0.5 * h, -0.5 * h, -0.5 * h};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        cx[q] = x + dx[q] * c - dy[q] * s;
-        cy[q] = y + dx[q] * s + dy[q] * c;
-    }
-}
-
-// Area of (quad 1) intersected with (quad 2): Sutherland-Hodgman, quad 1 clipped by the four edges of quad 2.  A convex
-// polygon gains at most one vertex per clip: 4 + 4 = 8.
-__device__ double quad_intersection_area(const double (&ax)[4], const double (&ay)[4], const double (&bx)[4], const double (&by)[4]) {
-    double px[10], py[10], qx[10], qy[10];
-    int n = 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        px[i] = ax[i];
-        py[i] = ay[i];
-    }
-    for (int e = 0; e < 4 && n > 0; ++e) {
-        const double ex0 = bx[e], ey0 = by[e], ex1 = bx[(e + 1) & 3], ey1 = by[(e + 1) & 3];
-        int m = 0;
-        for (int i = 0; i < n; ++i) {
-            const int j = (i + 1 == n) ? 0 : i + 1;
-            const double sp = (ex1 - ex0) * (py[i] - ey0) - (ey1 - ey0) * (px[i] - ex0);
-            const double sq = (ex1 - ex0) * (py[j] - ey0) - (ey1 - ey0) * (px[j] - ex0);
-            if (sp >= 0.0) {
-                qx[m] = px[i];
-                qy[m] = py[i];
-                ++m;
-            }
-            if ((sp >= 0.0) != (sq >= 0.0)) {
-                const double t = sp / (sp - sq);
-                qx[m] = px[i] + t * (px[j] - px[i]);
-                qy[m] = py[i] + t * (py[j] - py[i]);
-                ++m;
-            }
-        }
-        n = m;
-        for (int i = 0; i < n; ++i) {
-            px[i] = qx[i];
-            py[i] = qy[i];
-        }
-    }
-    if (n < 3) return 0.0;
-    double a2 = 0.0;
-    for (int i = 0; i < n; ++i) {
-        const int j = (i + 1 == n) ? 0 : i + 1;
-        a2 += px[i] * py[j] - px[j] * py[i];
-    }
-    return 0.5 * fabs(a2);
-}
-
-__device__ double rotated_iou_d(const float *a, const float *b) {
-    // A rectangle without area shares none with anything.  Not only a shortcut: all four edges of a POINT rectangle (w = h = 0) have
-    // zero length, every sp below is 0 and "inside", so clipping against it returned the whole of `a` -- inter = area(a) up to its
-    // rounding, uni = a rounding error, IoU = 0 or ~1e16 as the rounding fell.
-    if ((double)a[2] * a[3] == 0.0 || (double)b[2] * b[3] == 0.0) return 0.0;
-    double ax[4], ay[4], bx[4], by[4];
-    box_corners_d(a, ax, ay);
-    box_corners_d(b, bx, by);
-    // stand-up boxes first: disjoint -> 0 without clipping
-    double a0 = ax[0], a1 = ax[0], a2 = ay[0], a3 = ay[0], b0 = bx[0], b1 = bx[0], b2 = by[0], b3 = by[0];
-#pragma unroll
-    for (int q = 1; q < 4; ++q) {
-        a0 = fmin(a0, ax[q]); a1 = fmax(a1, ax[q]); a2 = fmin(a2, ay[q]); a3 = fmax(a3, ay[q]);
-        b0 = fmin(b0, bx[q]); b1 = fmax(b1, bx[q]); b2 = fmin(b2, by[q]); b3 = fmax(b3, by[q]);
-    }
-    if (a1 < b0 || b1 < a0 || a3 < b2 || b3 < a2) return 0.0;
-    const double inter = quad_intersection_area(ax, ay, bx, by);
-    const double uni = (double)a[2] * a[3] + (double)b[2] * b[3] - inter;   // |w*h| of each rectangle
-    return uni > 0.0 ? inter / uni : 0.0;
-}
+#include "det_geom.h"   // rotated-box IoU, stand-up box and the suppression test: shared with late_fuse.hip
 
 __global__ __launch_bounds__(256) void rotated_iou_kernel(const float *__restrict__ a, int na, const float *__restrict__ b, int nb,
                                                           float *__restrict__ iou) {
@@ -192,8 +113,7 @@ __global__ __launch_bounds__(256) void det_candidates_kernel(const float *__rest
 // 430 us for 400 candidates per map).  Maps with more candidates are marked NMS_PENDING and taken by the second launch (FAST = false,
 // `pending_only`: the serial scan with LDS for `cap` = up to 4096 candidates), which returns at once for every other map.
 // Same order, same overlap arithmetic, same decisions: identical detections.
-constexpr int NMS_PENDING = (int)0x80000000;
-constexpr int NMS_FAST_CAP = 512;
+// (NMS_PENDING, NMS_FAST_CAP: det_geom.h)
 
 template <bool ROTATED, bool SLOTTED = false, bool FAST = false>
 __global__ __launch_bounds__(256) void det_nms_kernel(const float *__restrict__ loc, const float *__restrict__ anchors,
@@ -254,22 +174,7 @@ __global__ __launch_bounds__(256) void det_nms_kernel(const float *__restrict__ 
         const float w = a[2] * expf(fminf(fmaxf(l[2], -4.0f), 4.0f));
         const float h = a[3] * expf(fminf(fmaxf(l[3], -4.0f), 4.0f));
         const float yaw = atan2f(a[4], a[5]) + atan2f(l[4], l[5]);
-        const float c = cosf(yaw), s = sinf(yaw);
-        // corners (+-w/2, +-h/2) rotated: x extents = |w/2*c| + |h/2*s| in exact arithmetic; numpy takes min/max of the four
-        // corners -- do the same so that the roundings agree
-        const float dx[4] = {w / 2, -w / 2, -w / 2, w / 2}, dy[4] = {h / 2, h / 2, -h / 2, -h / 2};
-        float x1 = 3.0e38f, y1 = 3.0e38f, x2 = -3.0e38f, y2 = -3.0e38f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            // separately rounded products and sums, in numpy's order (no FMA contraction)
-            const float cx = __fsub_rn(__fadd_rn(x, __fmul_rn(dx[q], c)), __fmul_rn(dy[q], s));
-            const float cy = __fadd_rn(__fadd_rn(y, __fmul_rn(dx[q], s)), __fmul_rn(dy[q], c));
-            x1 = fminf(x1, cx);
-            x2 = fmaxf(x2, cx);
-            y1 = fminf(y1, cy);
-            y2 = fmaxf(y2, cy);
-        }
-        sbox[i] = make_float4(x1, y1, x2, y2);
+        sbox[i] = det_standup_box(x, y, w, h, yaw);   // min / max of the four corners, separately rounded products and sums (det_geom.h)
         float *o = stage + (size_t)i * 5;
         o[0] = x;
         o[1] = y;
@@ -288,19 +193,11 @@ __global__ __launch_bounds__(256) void det_nms_kernel(const float *__restrict__ 
             const int j0 = w << 6;
             if (j0 + 63 > i) {
                 const float4 bi = sbox[i];
-                const float area_i = (bi.z - bi.x) * (bi.w - bi.y);
                 for (int b = 0; b < 64; ++b) {
                     const int j = j0 + b;
                     if (j <= i || j >= cnt) continue;
                     // the serial form's arithmetic with (kept, candidate) = (i, j)
-                    const float4 bj = sbox[j];
-                    const float iw = fmaxf(0.0f, fminf(bi.z, bj.z) - fmaxf(bi.x, bj.x));
-                    const float ih = fmaxf(0.0f, fminf(bi.w, bj.w) - fmaxf(bi.y, bj.y));
-                    const float inter = iw * ih;
-                    const float area_j = (bj.z - bj.x) * (bj.w - bj.y);
-                    bool sup;
-                    if constexpr (ROTATED) sup = inter > 0.0f && (float)rotated_iou_d(stage + (size_t)i * 5, stage + (size_t)j * 5) > nms_thr;
-                    else sup = inter / (area_i + area_j - inter + 1e-12f) > nms_thr;
+                    const bool sup = det_suppresses<ROTATED>(bi, sbox[j], stage + (size_t)i * 5, stage + (size_t)j * 5, nms_thr);
                     if (sup) bits |= 1ull << b;
                 }
             }
@@ -325,24 +222,12 @@ __global__ __launch_bounds__(256) void det_nms_kernel(const float *__restrict__ 
     // greedy scan
     for (int i = 0; i < cnt; ++i) {
         const float4 bi = sbox[i];
-        const float area_i = (bi.z - bi.x) * (bi.w - bi.y);
         const int nk = s_nkept;
         int sup = 0;
-        for (int k = tid; k < nk; k += 256) {
-            const float4 bk = sbox[skept[k]];
-            const float iw = fmaxf(0.0f, fminf(bk.z, bi.z) - fmaxf(bk.x, bi.x));
-            const float ih = fmaxf(0.0f, fminf(bk.w, bi.w) - fmaxf(bk.y, bi.y));
-            const float inter = iw * ih;
-            const float area_k = (bk.z - bk.x) * (bk.w - bk.y);
-            const float iou = inter / (area_k + area_i - inter + 1e-12f);
-            if constexpr (ROTATED) {
-                // rotated mode: the stand-up overlap is only the cheap reject; the decision is the polygon IoU of the decoded
-                // boxes (staged in global memory in sorted order)
-                if (inter > 0.0f && (float)rotated_iou_d(stage + (size_t)skept[k] * 5, stage + (size_t)i * 5) > nms_thr) sup = 1;
-            } else {
-                if (iou > nms_thr) sup = 1;
-            }
-        }
+        // rotated mode: the stand-up overlap is only the cheap reject; the decision is the polygon IoU of the decoded boxes (staged in global
+        // memory in sorted order)
+        for (int k = tid; k < nk; k += 256)
+            if (det_suppresses<ROTATED>(sbox[skept[k]], bi, stage + (size_t)skept[k] * 5, stage + (size_t)i * 5, nms_thr)) sup = 1;
         sup = __syncthreads_or(sup);
         if (!sup && tid == 0) {
             skept[nk] = i;

@@ -1,5 +1,5 @@
 """Row f-1 (post-processing and metric): python wrappers over v2x_det_postprocess[_rotated], the fused candidate heads + v2x_det_nms_candidates,
-v2x_rotated_iou and v2x_match_detections.  Re-exported by ops.py (`ops.det_postprocess` ...)."""
+v2x_det_late_fuse, v2x_rotated_iou and v2x_match_detections.  Re-exported by ops.py (`ops.det_postprocess` ...)."""
 import ctypes as C
 
 import torch
@@ -88,6 +88,36 @@ def det_nms_candidates(keys, codes, counts, anchors, nms_thr=0.01, rotated=False
                                           _dev(index, torch.int32, "index"), _dev(count, torch.int32, "count"), _stream()),
                "v2x_det_nms_candidates")
     return boxes, scores, index, count
+
+
+def late_fuse(boxes, scores, counts, rigid, link, extents, nms_thr=0.01, rotated=False, cap_out=None):
+    """Late fusion in one call (v2x_det_late_fuse): boxes (A*B, cap_in, 5), scores (A*B, cap_in), counts (A*B,) as det_postprocess / det_nms_candidates
+    leave them on the device (rows agent-major), rigid (B, A, A, 8) fp32 (utils/postprocess.late_rigid_from_trans), link (B, A, A) uint8 or bool,
+    extents ((x_lo, x_hi), (y_lo, y_hi), ...) -> (boxes (A*B, cap_out, 5), scores (A*B, cap_out), src (A*B, cap_out) int32 = j*cap_in + rank,
+    count (A*B,) int32; negative: not computed, see include/v2x_amd.h)."""
+    lib = _lib.load()
+    B, A = link.shape[0], link.shape[1]
+    n, cap_in = scores.shape
+    if n != A * B or tuple(rigid.shape) != (B, A, A, 8) or tuple(link.shape) != (B, A, A) or tuple(boxes.shape) != (n, cap_in, 5) or counts.numel() != n:
+        raise ValueError("late_fuse: boxes %s, scores %s, counts %s do not match rigid %s / link %s" % (tuple(boxes.shape), tuple(scores.shape),
+                                                                                                 tuple(counts.shape), tuple(rigid.shape), tuple(link.shape)))
+    cap_out = cap_in if cap_out is None else int(cap_out)
+    dev = boxes.device
+    if link.dtype == torch.bool:
+        link = link.to(torch.uint8)
+    out_boxes = torch.empty((n, cap_out, 5), dtype=torch.float32, device=dev)
+    out_scores = torch.empty((n, cap_out), dtype=torch.float32, device=dev)
+    out_src = torch.empty((n, cap_out), dtype=torch.int32, device=dev)
+    out_count = torch.empty((n,), dtype=torch.int32, device=dev)
+    (x_lo, x_hi), (y_lo, y_hi) = extents[0], extents[1]
+    _lib.check(lib.v2x_det_late_fuse(_dev(boxes, torch.float32, "boxes") if n else None, _dev(scores, torch.float32, "scores") if n else None,
+                                     _dev(counts, torch.int32, "counts") if n else None, A, B, cap_in,
+                                     _dev(rigid, torch.float32, "rigid") if n else None, _dev(link, torch.uint8, "link") if n else None,
+                                     C.c_float(x_lo), C.c_float(x_hi), C.c_float(y_lo), C.c_float(y_hi), C.c_float(nms_thr), int(bool(rotated)), cap_out,
+                                     _dev(out_boxes, torch.float32, "out_boxes") if n else None, _dev(out_scores, torch.float32, "out_scores") if n else None,
+                                     _dev(out_src, torch.int32, "out_src") if n else None, _dev(out_count, torch.int32, "out_count") if n else None,
+                                     _stream()), "v2x_det_late_fuse")
+    return out_boxes, out_scores, out_src, out_count
 
 
 def rotated_iou(boxes_a, boxes_b):

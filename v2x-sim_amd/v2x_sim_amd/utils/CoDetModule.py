@@ -28,6 +28,17 @@ class FaFModule(object):
         self.fused_detection = True       # with device_postprocess: score threshold in the heads' epilogue, logits never stored
         self.cap = 4096                   # candidate capacity per map of the device path
         self._anchors_dev = None
+        # late fusion (upstream --com late): the agents exchange their detections, every ego suppresses the union in its own frame (one more
+        # launch behind the per-agent NMS, ops.late_fuse).  Who hears whom: set_link_mask / late_only_v2i, the agent table and the empty sweeps.
+        self.late_fusion = False
+        self.late_only_v2i = False        # vehicles hear the road-side unit (agent 0) only, agent 0 hears everybody
+        self.late_cap = None              # merged capacity per ego of the device path (None: self.cap)
+        self._late_link = None
+        self.late_stats = {"egos": 0, "kept": 0, "from_neighbours": 0}    # counted by predict_all under late_fusion
+        from . import comm
+        flags = comm.current_model_flags() or {}
+        if flags.get("late"):             # built inside comm.model_flags(late=True): tools/det/eval_codet.py --com late
+            self.late_fusion, self.late_only_v2i, self.late_stats = True, bool(flags.get("only_v2i")), flags["late_stats"]
         # oracle/ASSUMPTIONS.md rows 48 / 49 as switches (configs.Config): which box extent runs along the heading, the loss normaliser
         self.wh_axis = getattr(config, "box_wh_axis", "w_along_heading")
         self.loss_normalizer = getattr(config, "loss_normalizer", "positives")
@@ -85,12 +96,68 @@ class FaFModule(object):
             return False
         return all(g.get("capturable", True) for g in self.optimizer.param_groups)
 
-    def postprocess(self, result):
+    def set_link_mask(self, mask):
+        """Late fusion's "who hears whom": (B, A, A) bool, entry [b, i, j] = ego i of frame b receives agent j's boxes; a false diagonal entry
+        takes agent i out of the frame.  None: everybody hears everybody.  late_only_v2i and the agent table are applied on top."""
+        self._late_link = None if mask is None else np.asarray(mask.cpu().numpy() if hasattr(mask, "cpu") else mask).astype(bool)
+
+    def late_links(self, data, batch_size, num_agent):
+        """-> (B, A, A) bool on the host: the user's mask, only_v2i and the agent table ('num_agent' (B, A): the agents of frame b are 0 .. n_b - 1)
+        folded; the empty sweeps are not in it (predict_all folds them on the device and through its None slots)."""
+        A, B = num_agent, batch_size
+        L = np.ones((B, A, A), bool) if self._late_link is None else self._late_link.copy()
+        if L.shape != (B, A, A):
+            raise ValueError("late fusion: the link mask is %s, the batch needs %s" % (L.shape, (B, A, A)))
+        if self.late_only_v2i:
+            v = np.eye(A, dtype=bool)
+            v[:, 0] = True
+            v[0, :] = True
+            L &= v
+        nat = data.get("num_agent")
+        if nat is not None:
+            n = np.asarray(nat.cpu().numpy() if hasattr(nat, "cpu") else nat).reshape(B, -1)[:, 0]
+            here = np.arange(A)[None, :] < n[:, None]
+            L &= here[:, :, None] & here[:, None, :]
+        return L
+
+    def _late_counted(self, seq_results):
+        for k, row in enumerate(seq_results):
+            for det in row:
+                if det is not None:
+                    self.late_stats["egos"] += 1
+                    self.late_stats["kept"] += len(det["src_agent"])
+                    self.late_stats["from_neighbours"] += int((det["src_agent"] != k).sum())
+        return seq_results
+
+    def _late_fused(self, boxes, scores, count, late):
+        """The fused launch behind the per-agent NMS, before the extents are un-swapped.  -> (per-agent count on the host, fused lists or None when
+        an ego was not computed: the caller takes the numpy path).  Copies: the two count vectors as one, then boxes and scores | sources."""
+        from .. import ops
+        rigid, link = late
+        fb, fs, fsrc, fcount = ops.late_fuse(boxes.contiguous(), scores, count, rigid, link, self.config.area_extents, self.nms_thr,
+                                             cap_out=self.late_cap or boxes.shape[1])
+        both = torch.stack([count, fcount]).cpu().numpy()
+        count_h, fcount_h = both[0], both[1]
+        if (count_h < 0).any() or (fcount_h < 0).any():
+            return count_h, None
+        kmax = int(max(1, fcount_h.max()))
+        swap = self.wh_axis == "h_along_heading"
+        fb = (fb[:, :kmax][..., [0, 1, 3, 2, 4]] if swap else fb[:, :kmax]).cpu().numpy()
+        ss = torch.cat([fs[:, :kmax], fsrc[:, :kmax].view(torch.float32)], 1).cpu().numpy()
+        fs_h, src_h = ss[:, :kmax], np.ascontiguousarray(ss[:, kmax:]).view(np.int32)
+        cap_in = boxes.shape[1]
+        return count_h, [{"boxes": fb[r, :fcount_h[r]], "scores": fs_h[r, :fcount_h[r]], "src_agent": (src_h[r, :fcount_h[r]] // cap_in).astype(np.int64),
+                          "corners": postprocess.box_corners(fb[r, :fcount_h[r]], self.wh_axis) if fcount_h[r] else np.zeros((0, 4, 2), np.float32)}
+                         for r in range(boxes.shape[0])]
+
+    def postprocess(self, result, late=None):
         """Device-side score / threshold / decode / NMS (v2x_det_postprocess) for every map of `result` -> list of
         dict(boxes, corners, scores) like postprocess.apply_nms_det; maps with more than `cap` candidates fall back to the
         host function (with random weights tens of thousands of anchors can pass the threshold).
         result = {'det': ...} (the heads already thresholded, DetModelBase.detections): only sort + decode + NMS are left;
-        -> None if a map overflowed `cap` there (the caller re-runs the logits path: no logits exist to fall back on)."""
+        -> None if a map overflowed `cap` there (the caller re-runs the logits path: no logits exist to fall back on).
+        late = (rigid (B, A, A, 8), link (B, A, A) uint8) on the device: the late-fusion launch is chained behind the NMS and the return value is
+        the pair (per-agent lists or None, fused lists or None) -- the fused lists when every ego was computed, the per-agent ones otherwise."""
         from .. import ops
         dev = (result["det"][0] if "det" in result else result["cls"]).device
         # "h_along_heading": the kernels lay w along the heading; a box with the extents exchanged is what they compute from anchors with
@@ -107,20 +174,30 @@ class FaFModule(object):
         if "det" in result:
             keys, codes, counts = result["det"]
             boxes, scores, _, count = ops.det_nms_candidates(keys, codes[..., perm].contiguous() if swap else codes, counts, self._anchors_dev, self.nms_thr)
+            fused = None
+            if late is not None:
+                count, fused = self._late_fused(boxes, scores, count, late)
+                if fused is not None:
+                    return None, fused
             boxes = unswap(boxes)
-            count = count.cpu().numpy()
+            count = count.cpu().numpy() if late is None else count
             if (count < 0).any():
                 return None
             kmax = int(max(1, count.max()))
             boxes, scores = boxes[:, :kmax].cpu().numpy(), scores[:, :kmax].cpu().numpy()
-            return [{"boxes": boxes[i, :count[i]], "scores": scores[i, :count[i]],
-                     "corners": postprocess.box_corners(boxes[i, :count[i]], self.wh_axis) if count[i] else np.zeros((0, 4, 2), np.float32)}
-                    for i in range(keys.shape[0])]
+            out = [{"boxes": boxes[i, :count[i]], "scores": scores[i, :count[i]],
+                    "corners": postprocess.box_corners(boxes[i, :count[i]], self.wh_axis) if count[i] else np.zeros((0, 4, 2), np.float32)}
+                   for i in range(keys.shape[0])]
+            return out if late is None else (out, None)
         cls, loc = result["cls"], result["loc"]
         boxes, scores, _, count = ops.det_postprocess(cls.contiguous(), (loc.reshape(cls.shape[0], -1, 6)[..., perm] if swap else loc).contiguous(), self._anchors_dev,
                                                       self.score_thr, self.nms_thr, self.cap)
+        if late is not None:
+            count, fused = self._late_fused(boxes, scores, count, late)
+            if fused is not None:
+                return None, fused
         boxes = unswap(boxes)
-        count = count.cpu().numpy()
+        count = count.cpu().numpy() if late is None else count
         kmax = int(max(1, count.max()))
         boxes, scores = boxes[:, :kmax].cpu().numpy(), scores[:, :kmax].cpu().numpy()
         out = []
@@ -132,7 +209,7 @@ class FaFModule(object):
             b = boxes[i, :count[i]]
             out.append({"boxes": b, "corners": postprocess.box_corners(b, self.wh_axis) if count[i] else np.zeros((0, 4, 2), np.float32),
                         "scores": scores[i, :count[i]]})
-        return out
+        return out if late is None else (out, None)
 
     def predict_all(self, data, batch_size, validation=True, num_agent=5, inference="activated"):
         """data: dict with 'bev_seq' (A*B, 1, X, Y, Z), 'trans_matrices' (B, A, A, 4, 4),
@@ -151,11 +228,26 @@ class FaFModule(object):
                     return self.model(bev_seq, data["trans_matrices"], data["num_agent"], batch_size=batch_size)
                 return self.model(bev_seq)
         dets = None
+        late = links = fused = None
+        post = self.postprocess
+        if self.late_fusion:
+            # who hears whom: the host's table (mask, only_v2i, agent table) and, folded in ON THE DEVICE, the empty sweeps -- no copy waits here
+            links = self.late_links(data, batch_size, num_agent)
+            if self.device_postprocess:
+                occ = (bev_seq.reshape(bev_seq.shape[0], -1) != 0).any(dim=1).reshape(num_agent, batch_size).t()          # (B, A)
+                link_dev = torch.from_numpy(links).to(bev_seq.device) & occ[:, :, None] & occ[:, None, :]
+                T = data["trans_matrices"]
+                if isinstance(T, torch.Tensor) and T.is_cuda:      # the same derivation where the matrices are: no device-to-host copy is added
+                    rigid = postprocess.late_rigid_from_trans_torch(T)
+                else:
+                    rigid = torch.from_numpy(postprocess.late_rigid_from_trans(T)).to(bev_seq.device)
+                late = (rigid.contiguous(), link_dev.to(torch.uint8).contiguous())
+                post = lambda r: self.postprocess(r, late)      # noqa: E731
         if self.device_postprocess and self.fused_detection and hasattr(self.model, "detections"):
             # detections without the logits round trip: the heads' epilogue thresholds the scores (DetModelBase.detections)
             with self.model.detections(self.score_thr, self.cap):
                 result = run()
-            dets = self.postprocess(result) if "det" in result else None
+            dets = post(result) if "det" in result else None
             if dets is None and "det" in result:
                 result = run()              # a map overflowed the candidate capacity: the logits path and its host fallback
         else:
@@ -163,7 +255,14 @@ class FaFModule(object):
         occupied = (bev_seq.reshape(bev_seq.shape[0], -1) != 0).any(dim=1).cpu().numpy()
         seq_results = [[] for _ in range(num_agent)]
         if dets is None:
-            dets = self.postprocess(result) if self.device_postprocess else None
+            dets = post(result) if self.device_postprocess else None
+        if late is not None:
+            dets, fused = dets
+        if fused is not None:
+            # every ego came out of the fused launch; a slot is None where the agent is absent (mask, agent table) or its sweep empty
+            self.last_result = result
+            return None, None, None, self._late_counted([[fused[k * batch_size + b] if occupied[k * batch_size + b] and links[b, k, k] else None
+                                                          for b in range(batch_size)] for k in range(num_agent)])
         if dets is None:
             cls = result["cls"].float().cpu().numpy()
             loc = result["loc"].float().cpu().numpy()
@@ -176,4 +275,9 @@ class FaFModule(object):
                 seq_results[k].append(dets[row] if dets is not None else
                                       postprocess.apply_nms_det(loc[row], cls[row], self.anchors, self.score_thr, self.nms_thr))
         self.last_result = result
+        if self.late_fusion:
+            # the numpy mirror: device_postprocess off, or an ego the fused launch did not compute (a map or the merged list beyond its capacity)
+            seq_results = postprocess.late_fusion(seq_results, data["trans_matrices"], num_agent, self.config.area_extents, link=links,
+                                                  nms_thr=self.nms_thr, wh_axis=self.wh_axis)
+            self._late_counted(seq_results)
         return None, None, None, seq_results

@@ -120,6 +120,96 @@ def apply_nms_det(loc, cls, anchors, score_thr=0.7, nms_thr=0.01, max_out=None, 
     return {"boxes": boxes[keep], "corners": corners[keep], "scores": score[sel][keep]}
 
 
+# ------------------------------------------------------------------ late fusion (upstream test_codet.py --com late)
+def _late_rigid_fields(T, atan2, stack, zeros_like):
+    """THE pose convention of late fusion, written once for numpy and torch: T (..., 4, 4) float64 in the WARP's axis convention (the dataset's
+    trans_matrices: T03 = -t_y, T13 = t_x, synthetic_scene.make_scene) -> (..., 8) float64 (r00, r01, tx, r10, r11, ty, dyaw, 0)."""
+    return stack([T[..., 0, 0], T[..., 0, 1], T[..., 1, 3], T[..., 1, 0], T[..., 1, 1], -T[..., 0, 3], atan2(T[..., 1, 0], T[..., 0, 0]),
+                  zeros_like(T[..., 0, 0])], -1)
+
+
+def late_rigid_from_trans(trans_matrices):
+    """trans_matrices (..., 4, 4), the dataset's (entry [b, i, j] = the pose of agent j w.r.t. ego i) -> (..., 8) fp32 numpy: the box transform
+    of v2x_det_late_fuse, derived on the host in float64 and rounded once."""
+    T = np.asarray(trans_matrices.detach().cpu().numpy() if hasattr(trans_matrices, "detach") else trans_matrices, dtype=np.float64)
+    return _late_rigid_fields(T, np.arctan2, np.stack, np.zeros_like).astype(np.float32)
+
+
+def late_rigid_from_trans_torch(trans_matrices):
+    """The same derivation where a torch tensor lives (FaFModule.predict_all: the matrices are already on the device and no device-to-host copy
+    is to be added): float64, rounded once, -> (..., 8) fp32 tensor on that device.  Seven of the eight fields are copies or a negation; dyaw is
+    torch.atan2 in float64, which tests/test_late_refs_cpu.py (CPU tensors) and tests/test_gpu_late_fuse.py (the device) hold bit-equal to
+    late_rigid_from_trans after the rounding to fp32 on their seeded poses ("late fusion")."""
+    import torch
+    return _late_rigid_fields(trans_matrices.to(torch.float64), torch.atan2, torch.stack, torch.zeros_like).to(torch.float32)
+
+
+def late_transform(boxes, rigid8):
+    """(N, 5) fp32 boxes of a neighbour, (8,) fp32 rigid -> (N, 5) fp32 in the ego's frame: numpy's separate float32 operations, which are the
+    kernel's (__fmul_rn / __fadd_rn), bit for bit."""
+    b = np.asarray(boxes, np.float32).reshape(-1, 5)
+    r = np.asarray(rigid8, np.float32)
+    out = b.copy()
+    out[:, 0] = (r[0] * b[:, 0] + r[1] * b[:, 1]) + r[2]
+    out[:, 1] = (r[3] * b[:, 0] + r[4] * b[:, 1]) + r[5]
+    out[:, 4] = b[:, 4] + r[6]
+    return out
+
+
+def late_candidates(boxes_of, scores_of, ego, rigid_row, link_row, extents):
+    """The merged candidate list of one ego, ungathered order: boxes_of[j] (N_j, 5), scores_of[j] (N_j,) fp32 per agent (None: no list),
+    rigid_row (A, 8), link_row (A,) -> boxes (N, 5) fp32, scores (N,) fp32, agent (N,), rank (N,).  The ego's own enter as they are; a neighbour's
+    are transformed and cropped to x_lo <= x' < x_hi, y_lo <= y' < y_hi; non-finite fields and scores not >= 0 drop a candidate."""
+    (x_lo, x_hi), (y_lo, y_hi) = (np.float32(v) for v in extents[0]), (np.float32(v) for v in extents[1])
+    bs, ss, ag, rk = [np.zeros((0, 5), np.float32)], [np.zeros((0,), np.float32)], [np.zeros((0,), np.int64)], [np.zeros((0,), np.int64)]
+    for j in range(len(link_row)):
+        if boxes_of[j] is None or (j != ego and not link_row[j]):
+            continue
+        src = np.asarray(boxes_of[j], np.float32).reshape(-1, 5)
+        sc = np.asarray(scores_of[j], np.float32).reshape(-1)
+        with np.errstate(all="ignore"):
+            b = src.copy() if j == ego else late_transform(src, rigid_row[j])
+            ok = np.isfinite(src).all(1) & np.isfinite(b).all(1) & np.isfinite(sc) & (sc >= 0)
+            if j != ego:
+                ok &= (b[:, 0] >= x_lo) & (b[:, 0] < x_hi) & (b[:, 1] >= y_lo) & (b[:, 1] < y_hi)
+        w = np.nonzero(ok)[0]
+        bs.append(b[w]), ss.append(sc[w]), ag.append(np.full(w.shape, j, np.int64)), rk.append(w)
+    return np.concatenate(bs), np.concatenate(ss), np.concatenate(ag), np.concatenate(rk)
+
+
+def late_order(scores, agent, rank, ego):
+    """Score descending; ties: the ego's own boxes, then neighbours by ascending agent index, then ascending rank in the source list."""
+    return np.lexsort((rank, np.where(agent == ego, -1, agent), -np.asarray(scores, np.float64)))
+
+
+def late_fusion(seq_dets, trans_matrices, num_agent, extents, link=None, nms_thr=0.01, wh_axis="w_along_heading"):
+    """The numpy mirror of v2x_det_late_fuse on FaFModule.predict_all's per-agent results: seq_dets[k][b] = dict(boxes, scores, ...) or None,
+    trans_matrices (B, A, A, 4, 4), link (B, A, A) or None (everybody hears everybody) -> the same nest with, per present ego, dict(boxes,
+    corners, scores, src_agent): its own detections and its linked neighbours' in its frame, cropped to `extents`, after one more stand-up NMS
+    in fp32 (nms_standup: what the kernel mirrors).  Agents whose slot is None are absent: they send nothing and get None."""
+    A = num_agent
+    Bn = len(seq_dets[0]) if A else 0
+    rigid = late_rigid_from_trans(trans_matrices)
+    swap = wh_axis == "h_along_heading"            # the kernels' boxes carry w along the heading: exchange, fuse, exchange back
+    out = [[None] * Bn for _ in range(A)]
+    for b in range(Bn):
+        boxes_of = [None if seq_dets[j][b] is None else np.asarray(seq_dets[j][b]["boxes"], np.float32).reshape(-1, 5)[:, [0, 1, 3, 2, 4] if swap else slice(None)]
+                    for j in range(A)]
+        scores_of = [None if seq_dets[j][b] is None else seq_dets[j][b]["scores"] for j in range(A)]
+        for i in range(A):
+            if boxes_of[i] is None or (link is not None and not link[b][i][i]):
+                continue
+            row = np.ones(A, bool) if link is None else np.asarray(link[b][i]).astype(bool)
+            bx, sc, ag, rk = late_candidates(boxes_of, scores_of, i, rigid[b, i], row, extents)
+            order = late_order(sc, ag, rk, i)
+            bx, sc, ag = bx[order], sc[order], ag[order]
+            keep = nms_standup(standup(box_corners(bx)), -np.arange(len(sc), dtype=np.float64), nms_thr) if len(sc) else np.zeros(0, np.int64)
+            kb = bx[keep][:, [0, 1, 3, 2, 4]] if swap else bx[keep]
+            out[i][b] = {"boxes": kb, "corners": box_corners(kb, wh_axis) if len(keep) else np.zeros((0, 4, 2), np.float32), "scores": sc[keep],
+                         "src_agent": ag[keep]}
+    return out
+
+
 # ------------------------------------------------------------------ rotated IoU + AP
 def _poly_area(p):
     x, y = p[:, 0], p[:, 1]
