@@ -593,6 +593,30 @@ int v2x_det_late_fuse(const float *boxes, const float *scores, const int32_t *co
                       float nms_thr, int rotated, int cap_out, float *out_boxes, float *out_scores,
                       int32_t *out_src, int32_t *out_count, v2x_stream_t stream);
 
+/* f-3: detection training targets -- anchors assigned to ground-truth boxes by rotated IoU with thresholds (upstream assigns when the data is created
+ * and stores gt_max_iou; DESIGN.md section 3.7 "IoU assignment" is the frozen rule).  All n_items items of the call in two launches (a workgroup per
+ * 16 x 16 tile of cells and item, then a workgroup per item); no atomics, no allocation, no host synchronisation, capturable; EVERY output element is
+ * written, the caller clears nothing.
+ * gt_boxes fp32 [n_items][gt_cap][5] (x, y, w, h, yaw), gt_count int32 [n_items] (clamped to [0, gt_cap]), gt_cap in [1, 256].  A box with a non-finite
+ *   field or a negative extent is dropped; a zero extent is valid and has IoU 0 with everything (v2x_rotated_iou's rule).
+ * anchors fp32 [X][Y][A][6] (x, y, w, h, sin, cos): the anchor's box is (x, y, w, h, yaw_a), yaw_a = the fp32 rounding of atan2(sin, cos) in fp64.
+ * 0 < neg_thr <= pos_thr <= 1, compared as their fp32 values with the fp64 IoU.  Per anchor q: g* = the valid box of largest IoU (lowest index on ties),
+ *   miou that IoU; no box with IoU > 0: g* = -1, miou = 0.  miou >= pos_thr: label (0, 1), mask 1, assoc g*, the code of (q, g*); miou < neg_thr: label
+ *   (1, 0), mask 0, assoc -1, code 0; otherwise IGNORED: label (0, 0), mask 0, assoc -1, code 0 (contributes to neither term of v2x_det_loss_forward).
+ * Per valid box g with gmax(g) = max over q of IoU(q, g) > 0: gt_max_iou = gmax, gt_best = the lowest flat index (ix*Y + iy)*A + a attaining it; every
+ *   other entry of the two (dropped boxes, gmax = 0, at or beyond the count) = 0 and -1.  force_match != 0: anchor gt_best[g] becomes positive for g
+ *   whatever the threshold step gave it; several boxes claiming one anchor: the largest IoU wins, the lowest g on ties (anchor_iou stays miou).
+ * Code = the inverse of the 'faf' decode: (gx - ax, gy - ay, log(gw/aw), log(gh/ah), sin d, cos d), d = gyaw - yaw_a folded to [-pi/2, pi/2), in fp64
+ *   from the fp32 inputs, rounded once.
+ * labels fp32 [n][X][Y][A][2], reg_targets fp32 [n][X][Y][A][1][6], reg_loss_mask uint8 [n][X][Y][A][1] (what v2x_det_loss_forward reads); assoc int32
+ * [n][X][Y][A] or NULL, anchor_iou fp32 [n][X][Y][A] or NULL; gt_max_iou fp32 [n][gt_cap], gt_best int32 [n][gt_cap].  labels and workspace 8-byte
+ * aligned; workspace_bytes >= v2x_det_assign_workspace_size (-1 for sizes out of range: X*Y*A and n_items*tiles must stay below 2^31).
+ * n_items == 0: nothing to do (V2X_OK). */
+long long v2x_det_assign_workspace_size(long long n_items, int X, int Y, int A, int gt_cap);
+int v2x_det_assign_targets(const float *gt_boxes, const int32_t *gt_count, long long n_items, int gt_cap, const float *anchors, int X, int Y, int A,
+                           float pos_thr, float neg_thr, int force_match, float *labels, float *reg_targets, uint8_t *reg_loss_mask, int32_t *assoc,
+                           float *anchor_iou, float *gt_max_iou, int32_t *gt_best, void *workspace, long long workspace_bytes, v2x_stream_t stream);
+
 /* ---------------------------------------------------------------- f-1: the metric (coperception/utils/mean_ap.py::eval_map)
  * Upstream intersects shapely polygons on the host; here the IoU of rotated boxes (x, y, w, h, yaw) is a convex clip in
  * fp64 on the device.

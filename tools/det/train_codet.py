@@ -39,6 +39,9 @@ def build_parser():
     ap.add_argument("--log", action="store_true")
     ap.add_argument("--nworker", default=0, type=int, help="DataLoader workers (parsed dataset)")
     ap.add_argument("--rsu", default=1, type=int, help="parsed dataset: 1 = agent0 (the RSU) takes part, 0 = vehicles only")
+    ap.add_argument("--targets", default="radius", choices=["radius", "iou"],
+                    help="anchor assignment (DESIGN.md section 3.7): radius = the 0.75 m centre rule, built on the host per item; iou = rotated IoU with "
+                         "thresholds and forced best match, one call on the GPU for all items of the step (v2x_det_assign_targets)")
     from v2x_sim_amd.utils import comm
     comm.add_arguments(ap)
     ap.add_argument("--engine", default="", choices=["", "torch", "hip", "hip-graph"],
@@ -104,10 +107,10 @@ def main(argv=None):
     for epoch in range(start, args.nepoch + 1):
         if dataset is not None:
             hist = train_dataset(model, config, dataset, 1, args.batch, args.lr, seed=args.seed + epoch,
-                                 log=20 if args.log else None, num_workers=args.nworker, opt=opt, sched=sched)
+                                 log=20 if args.log else None, num_workers=args.nworker, opt=opt, sched=sched, targets=args.targets)
         else:
             hist = train_synthetic(model, config, args.steps, args.batch, args.lr, seed=args.seed + epoch,
-                                   log=20 if args.log else None, opt=opt, sched=sched)
+                                   log=20 if args.log else None, opt=opt, sched=sched, targets=args.targets)
         tail = hist[-20:]
         print("epoch %d (lr %.2e): mean loss of the last %d steps %.4f" % (epoch, opt.param_groups[0]["lr"], len(tail),
                                                                            sum(h[0] for h in tail) / len(tail)))

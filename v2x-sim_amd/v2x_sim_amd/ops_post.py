@@ -1,7 +1,8 @@
 """Row f-1 (post-processing and metric): python wrappers over v2x_det_postprocess[_rotated], the fused candidate heads + v2x_det_nms_candidates,
-v2x_det_late_fuse, v2x_rotated_iou and v2x_match_detections.  Re-exported by ops.py (`ops.det_postprocess` ...)."""
+v2x_det_late_fuse, v2x_rotated_iou and v2x_match_detections; and the IoU anchor assignment of row f-3 (v2x_det_assign_targets), which shares their box geometry.  Re-exported by ops.py (`ops.det_postprocess` ...)."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _launch, _lib
@@ -118,6 +119,70 @@ def late_fuse(boxes, scores, counts, rigid, link, extents, nms_thr=0.01, rotated
                                      _dev(out_src, torch.int32, "out_src") if n else None, _dev(out_count, torch.int32, "out_count") if n else None,
                                      _stream()), "v2x_det_late_fuse")
     return out_boxes, out_scores, out_src, out_count
+
+
+ASSIGN_OUTPUTS = {"labels": (torch.float32, (2,)), "reg_targets": (torch.float32, (1, 6)), "reg_loss_mask": (torch.uint8, (1,)),
+                  "assoc": (torch.int32, ()), "anchor_iou": (torch.float32, ())}
+
+
+def assign_targets(gt_boxes, gt_count, anchors, pos_thr=0.6, neg_thr=0.45, force_match=True, want=("assoc", "anchor_iou"), out=None):
+    """Detection training targets by rotated IoU (v2x_det_assign_targets; the rule: DESIGN.md section 3.7 "IoU assignment").
+    gt_boxes (n, gt_cap, 5) fp32 (x, y, w, h, yaw), gt_count (n,) int32, anchors (X, Y, A, 6) fp32, all on the device ->
+    dict: labels (n, X, Y, A, 2) fp32, reg_targets (n, X, Y, A, 1, 6) fp32, reg_loss_mask (n, X, Y, A, 1) uint8 (what FaFModule.step reads),
+    gt_max_iou (n, gt_cap) fp32, gt_best (n, gt_cap) int32, and the optional outputs named in `want`: assoc (n, X, Y, A) int32, anchor_iou
+    (n, X, Y, A) fp32.  out: a dict of existing tensors to write into (any subset of the keys; e.g. the static buffers a captured step reads);
+    an optional output present in `out` is written too.  Every element of every output is written."""
+    lib = _lib.load()
+    n, gt_cap = int(gt_boxes.shape[0]), int(gt_boxes.shape[1])
+    X, Y, A = (int(v) for v in anchors.shape[:3])
+    if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 5 or gt_count.numel() != n or tuple(anchors.shape) != (X, Y, A, 6):
+        raise ValueError("assign_targets: gt_boxes %s, gt_count %s, anchors %s" % (tuple(gt_boxes.shape), tuple(gt_count.shape), tuple(anchors.shape)))
+    unknown = (set(want) - {"assoc", "anchor_iou"}) | (set(out or ()) - set(ASSIGN_OUTPUTS) - {"gt_max_iou", "gt_best"})
+    if unknown:
+        raise ValueError("assign_targets: unknown output %s" % sorted(unknown))
+    dev = gt_boxes.device
+    res = dict(out) if out is not None else {}
+
+    def buf(name, dtype, shape):
+        t = res.get(name)
+        if t is None:
+            t = res[name] = torch.empty(shape, dtype=dtype, device=dev)
+        elif tuple(t.shape) != tuple(shape) or (t.dtype != dtype and not (dtype == torch.uint8 and t.dtype == torch.bool)):
+            raise ValueError("assign_targets: out[%r] is %s %s, needs %s %s" % (name, t.dtype, tuple(t.shape), dtype, tuple(shape)))
+        return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+    ptr = {}
+    for name, (dtype, tail) in ASSIGN_OUTPUTS.items():
+        if name in ("assoc", "anchor_iou") and name not in want and name not in res:
+            ptr[name] = None
+            continue
+        t = buf(name, dtype, (n, X, Y, A) + tail)
+        ptr[name] = _dev(t, dtype, name) if n else None
+    gmax = buf("gt_max_iou", torch.float32, (n, gt_cap))
+    gbest = buf("gt_best", torch.int32, (n, gt_cap))
+    nbytes = lib.v2x_det_assign_workspace_size(n, X, Y, A, gt_cap)
+    if nbytes < 0:
+        raise ValueError("assign_targets: sizes out of range (n=%d, X=%d, Y=%d, A=%d, gt_cap=%d; gt_cap <= 256)" % (n, X, Y, A, gt_cap))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=dev)
+    _lib.check(lib.v2x_det_assign_targets(_dev(gt_boxes, torch.float32, "gt_boxes") if n else None, _dev(gt_count, torch.int32, "gt_count") if n else None,
+                                          n, gt_cap, _dev(anchors, torch.float32, "anchors"), X, Y, A, C.c_float(pos_thr), C.c_float(neg_thr),
+                                          int(bool(force_match)), ptr["labels"], ptr["reg_targets"], ptr["reg_loss_mask"], ptr["assoc"], ptr["anchor_iou"],
+                                          _dev(gmax, torch.float32, "gt_max_iou") if n else None, _dev(gbest, torch.int32, "gt_best") if n else None,
+                                          _dev(ws, torch.int64, "workspace"), nbytes, _stream()), "v2x_det_assign_targets")
+    return res
+
+
+def assign_targets_sparse_keys(res, item=0):
+    """One item of assign_targets' result -> the sparse training keys an upstream-produced 0.npy carries (datasets/V2XSimDet.UPSTREAM_TARGET_KEYS
+    + gt_max_iou), as host arrays: allocation_mask (X, Y, A) bool = the positive anchors, label_sparse (n_alloc,) int64 = 1, reg_target_sparse
+    (n_alloc, 1, 6) fp32, reg_loss_mask (X, Y, A, 1) bool, gt_max_iou (gt_cap,) fp32.  datasets.V2XSimDet.upstream_dense_targets turns them back
+    into the dense fields.  The format has no ignore state: an ignored anchor (label (0, 0)) reads back as background."""
+    labels = res["labels"][item].cpu().numpy()
+    reg = res["reg_targets"][item].cpu().numpy()
+    mask = res["reg_loss_mask"][item].cpu().numpy().astype(bool)
+    alloc = labels[..., 1] > 0
+    return {"allocation_mask": alloc, "label_sparse": np.ones((int(alloc.sum()),), np.int64), "reg_target_sparse": reg[alloc],
+            "reg_loss_mask": mask, "gt_max_iou": res["gt_max_iou"][item].cpu().numpy()}
 
 
 def rotated_iou(boxes_a, boxes_b):

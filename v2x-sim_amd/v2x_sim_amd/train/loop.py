@@ -32,18 +32,47 @@ def init_for_training(model, fg_prior=0.01, seed=0):
     return model
 
 
-def synthetic_batch_on_device(config, frames, agents, seed, device, grid=None, anchors=None, with_targets=True, **scene_kw):
-    """-> data dict in FaFModule.step / predict_all's format (+ 'gt_boxes'[agent][frame] host arrays)."""
+TARGET_RULES = ("radius", "iou")
+_ANCHORS_ON_DEVICE = {}
+
+
+def iou_targets_on_device(gt_lists, anchors, device, **assign_kw):
+    """The training targets of DESIGN.md section 3.7's IoU rule for a batch: gt_lists = one (G_m, 5) array of boxes per item, in the models' batch
+    order; padded to the longest list, uploaded once and assigned in ONE call (ops.assign_targets) -- no per-item work on the host.
+    -> (labels, reg_targets, reg_loss_mask bool) as dense_targets_on_device returns them."""
+    import numpy as np
+    cap = max(1, max(np.asarray(g).reshape(-1, 5).shape[0] for g in gt_lists))
+    boxes = np.zeros((len(gt_lists), cap, 5), np.float32)
+    count = np.zeros((len(gt_lists),), np.int32)
+    for m, g in enumerate(gt_lists):
+        g = np.asarray(g, np.float32).reshape(-1, 5)
+        boxes[m, :g.shape[0]], count[m] = g, g.shape[0]
+    key = (id(anchors), str(device))
+    if key not in _ANCHORS_ON_DEVICE or _ANCHORS_ON_DEVICE[key][0] is not anchors:
+        _ANCHORS_ON_DEVICE[key] = (anchors, torch.from_numpy(np.ascontiguousarray(anchors, np.float32)).to(device))
+    res = ops.assign_targets(torch.from_numpy(boxes).to(device), torch.from_numpy(count).to(device), _ANCHORS_ON_DEVICE[key][1], want=(), **assign_kw)
+    return res["labels"], res["reg_targets"], res["reg_loss_mask"].view(torch.bool)
+
+
+def synthetic_batch_on_device(config, frames, agents, seed, device, grid=None, anchors=None, with_targets=True, targets="radius", **scene_kw):
+    """-> data dict in FaFModule.step / predict_all's format (+ 'gt_boxes'[agent][frame] host arrays).
+    targets: the assignment rule -- "radius": positives built per item on the host and scattered on the device; "iou": the
+    padded boxes uploaded and assigned by rotated IoU in one call on the device (iou_targets_on_device)."""
+    if targets not in TARGET_RULES:
+        raise ValueError("targets must be one of %s" % (TARGET_RULES,))
     anchors = postprocess.build_anchor_map(config) if anchors is None else anchors
     grid = grid or ops.VoxelGrid(config.voxel_size, config.area_extents)
-    b = synthetic_scene.make_batch(frames, agents, seed=seed, anchors=anchors if with_targets else None, targets="sparse",
+    b = synthetic_scene.make_batch(frames, agents, seed=seed, anchors=anchors if with_targets and targets == "radius" else None, targets="sparse",
                                    **scene_kw)
     pts = torch.from_numpy(b["points"]).to(device)
     bits = ops.voxelize_bits(pts, torch.from_numpy(b["n_pts"]).to(device), grid)
     data = {"bev_seq": ops.bits_to_dense(bits, grid.dims[2])[:, None],
             "trans_matrices": torch.from_numpy(b["trans"]).to(device), "num_agent": torch.from_numpy(b["num_agent"]),
             "gt_boxes": b["gt_boxes"]}
-    if with_targets:
+    if with_targets and targets == "iou":
+        data["labels"], data["reg_targets"], data["reg_loss_mask"] = iou_targets_on_device(
+            [b["gt_boxes"][a][f] for a in range(agents) for f in range(frames)], anchors, device)
+    elif with_targets:
         data["labels"], data["reg_targets"], data["reg_loss_mask"] = synthetic_scene.dense_targets_on_device(
             b["pos"], b["pos_reg"], frames * agents, anchors.shape, device)
     return data
@@ -68,9 +97,10 @@ def make_optimizer(model, lr, total_steps):
 
 
 def train_synthetic(model, config, steps, frames_per_step=2, lr=1e-3, seed=0, device="cuda:0", log=None, agents=None,
-                    opt=None, sched=None, **scene_kw):
+                    opt=None, sched=None, targets="radius", **scene_kw):
     """Adam on freshly generated synthetic scenes (never the same scene twice).  -> list of (loss, cls, loc).
-    opt / sched: the run's optimizer and scheduler (make_optimizer); created here for a single self-contained run."""
+    opt / sched: the run's optimizer and scheduler (make_optimizer); created here for a single self-contained run.
+    targets: "radius" | "iou", see synthetic_batch_on_device."""
     agents = agents or model.agent_num
     device = torch.device(device)
     model.to(device)
@@ -81,7 +111,7 @@ def train_synthetic(model, config, steps, frames_per_step=2, lr=1e-3, seed=0, de
     hist = []
     for it in range(steps):
         data = synthetic_batch_on_device(config, frames_per_step, agents, seed * 1000003 + it, device, grid, module.anchors,
-                                         **scene_kw)
+                                         targets=targets, **scene_kw)
         hist.append(module.step(data, frames_per_step, agents))
         if sched is not None:
             sched.step()
@@ -91,13 +121,15 @@ def train_synthetic(model, config, steps, frames_per_step=2, lr=1e-3, seed=0, de
     return hist
 
 
-def dataset_batch_on_device(samples, grid, anchors, device):
+def dataset_batch_on_device(samples, grid, anchors, device, targets="radius"):
     """Parsed-dataset samples (datasets.V2XSimDet with densify='none': sparse voxel indices + poses + gt boxes) -> the
     data dict of FaFModule.step.  The sweep is densified on the GPU (v2x_indices_to_bits -> v2x_bits_to_dense_f32); the
     anchor targets upstream's Dataset would return (label_one_hot, reg_target, reg_loss_mask) are built from the stored
-    ground-truth boxes (synthetic_scene.anchor_targets_sparse, the assignment rule of DESIGN.md section 3.7) and scattered
-    on the device."""
+    ground-truth boxes (synthetic_scene.anchor_targets_sparse, the radius rule of DESIGN.md section 3.7) and scattered
+    on the device; targets="iou": assigned by rotated IoU on the device in one call (iou_targets_on_device)."""
     import numpy as np
+    if targets not in TARGET_RULES:
+        raise ValueError("targets must be one of %s" % (TARGET_RULES,))
     B, A = len(samples), len(samples[0])
     items = [(a, b) for a in range(A) for b in range(B)]                       # agent-major, as the models batch
     cap = max(1, max(samples[b][a][0].shape[0] for a, b in items))
@@ -108,22 +140,26 @@ def dataset_batch_on_device(samples, grid, anchors, device):
         it = samples[b][a][0]
         idx[m, :it.shape[0]] = it
         cnt[m] = it.shape[0]
-        p, r = synthetic_scene.anchor_targets_sparse(samples[b][a][12], anchors)
-        pos.append(np.concatenate([np.full((p.shape[0], 1), m, np.int64), p], 1))
-        reg.append(r)
+        if targets == "radius":
+            p, r = synthetic_scene.anchor_targets_sparse(samples[b][a][12], anchors)
+            pos.append(np.concatenate([np.full((p.shape[0], 1), m, np.int64), p], 1))
+            reg.append(r)
     bits = ops.indices_to_bits(torch.from_numpy(idx).to(device), torch.from_numpy(cnt).to(device), grid)
     data = {"bev_seq": ops.bits_to_dense(bits, grid.dims[2])[:, None],
             "trans_matrices": torch.from_numpy(np.stack([np.stack([samples[b][a][11] for a in range(A)])
                                                          for b in range(B)])).to(device),
             "num_agent": torch.tensor([[samples[b][a][10] for a in range(A)] for b in range(B)]),
             "gt_boxes": [[samples[b][a][12] for b in range(B)] for a in range(A)]}
-    data["labels"], data["reg_targets"], data["reg_loss_mask"] = synthetic_scene.dense_targets_on_device(
-        np.concatenate(pos), np.concatenate(reg), len(items), anchors.shape, device)
+    if targets == "iou":
+        data["labels"], data["reg_targets"], data["reg_loss_mask"] = iou_targets_on_device([samples[b][a][12] for a, b in items], anchors, device)
+    else:
+        data["labels"], data["reg_targets"], data["reg_loss_mask"] = synthetic_scene.dense_targets_on_device(
+            np.concatenate(pos), np.concatenate(reg), len(items), anchors.shape, device)
     return data
 
 
 def train_dataset(model, config, dataset, epochs=1, batch=2, lr=1e-3, seed=0, device="cuda:0", log=None, num_workers=0,
-                  opt=None, sched=None):
+                  opt=None, sched=None, targets="radius"):
     """Adam over a parsed dataset (datasets.V2XSimDet, densify='none'), shuffled per epoch; upstream's
     train_codet.py loop with the densify and the target scatter moved to the GPU.  -> list of (loss, cls, loc) per step.
     opt / sched as in train_synthetic."""
@@ -143,7 +179,7 @@ def train_dataset(model, config, dataset, epochs=1, batch=2, lr=1e-3, seed=0, de
     hist = []
     for ep in range(epochs):
         for samples in loader:
-            data = dataset_batch_on_device(samples, grid, module.anchors, device)
+            data = dataset_batch_on_device(samples, grid, module.anchors, device, targets=targets)
             hist.append(module.step(data, len(samples), len(samples[0])))
             if sched is not None:
                 sched.step()
