@@ -679,6 +679,34 @@ size_t v2x_hota_workspace_size(int n_seq, int n_frames, int cap, int n_gt_ids, i
 int v2x_hota_sequences(const float *gt_boxes, const int32_t *gt_ids, const int32_t *gt_count, const float *trk_boxes, const int32_t *trk_ids,
                        const int32_t *trk_count, int n_seq, int n_frames, int cap, int n_gt_ids, int n_trk_ids, const double *alpha, int n_alpha,
                        void *workspace, size_t workspace_bytes, int32_t *out_i, double *out_f, v2x_stream_t stream);
+/* v2x_mot_sequences: the CLEAR MOT family and the Identity family (TrackEval's clear.py and identity.py) of n_seq padded
+ * sequences in FIVE launches whatever n_seq and n_frames are, no host round trip (capturable), no atomics: a sequence's outputs are bit-identical
+ * alone and in any batch, whatever the padding of frames, boxes and ids.
+ * INPUT: v2x_hota_sequences' layout and reading, unchanged -- gt_boxes fp32 [n_seq][n_frames][cap][4] (x1, y1, x2, y2; 16-byte aligned), gt_ids
+ *   int32 [n_seq][n_frames][cap], gt_count int32 [n_seq][n_frames] (clamped to [0, cap]); the same for the tracks.  cap in [1, 64].  Ids are per
+ *   sequence and contiguous, 0 .. n_gt_ids - 1 / 0 .. n_trk_ids - 1; a box whose id lies outside is absent everywhere.  n_gt_ids and n_trk_ids
+ *   in [0, 2048]: the id cap (one workgroup's LDS holds the assignment over a sequence's id space); beyond it the size query returns 0.
+ *   An id twice in one frame is a caller error: unspecified result, memory-safe and terminating.
+ * Similarity S = the IoU of the axis-aligned boxes in fp64 on the fp32 coordinates, operation by operation; a NaN or infinite value reads as 0.
+ * CLEAR, frames in order: a frame without ground truth or without tracks adds its boxes to FN / FP and clears the previous-frame matches.
+ *   Otherwise score = 1000 [the ground-truth id's track id in the previous frame's matches == this track id] + S, entries with S < thr - 2^-52
+ *   zeroed, the maximum-sum assignment in fp64 (nothing is rounded to fp32), a pair is matched when its score > 0.  TP, FN, FP accumulate;
+ *   MOTP_sum = the matched S, added in frame order, then slot order; IDSW counts a matched id whose last matched track id, any frame back,
+ *   exists and differs.  Per ground-truth id: present (frames with a valid box, frames without tracks included), matched, starts (matched and
+ *   not in the previous frame's matches).  Over the ids with present > 0, in integers: MT = #{5 matched > 4 present}, PT = #{5 matched >=
+ *   present} - MT, ML = #{present > 0} - MT - PT, Frag = sum of max(0, starts - 1).  An id that never occurs counts for nothing.
+ * IDENTITY: pmc[g][k] = frames in which g and k are both present with S >= thr (plain fp64 comparison, no epsilon); IDTP = the maximum over
+ *   partial one-to-one matchings of ids of the summed pmc (an optimal assignment, never a greedy one; the weights are integers, so the value is
+ *   unique), IDFN = the ground-truth boxes - IDTP, IDFP = the track boxes - IDTP.
+ * thr: finite.  workspace: DEVICE, 16-byte aligned, workspace_bytes >= v2x_mot_workspace_size(the same five sizes) (0: sizes out of range, an
+ *   id space beyond the cap or an overflow); it needs no initialisation and holds nothing the caller needs afterwards.
+ * OUTPUT per sequence: out_i int32 [n_seq][11] = TP, FN, FP, IDSW, MT, PT, ML, Frag, IDTP, IDFN, IDFP; out_f fp64 [n_seq][1] = MOTP_sum.
+ *   MOTA, MOTP, IDF1 ... and the combination over sequences follow on the host (v2x_sim_amd/utils/mot_metrics.py::ClearIdentity).
+ *   n_seq x n_frames and n_seq x n_gt_ids x ceil(n_trk_ids / 64) <= 2^24. */
+size_t v2x_mot_workspace_size(int n_seq, int n_frames, int cap, int n_gt_ids, int n_trk_ids);
+int v2x_mot_sequences(const float *gt_boxes, const int32_t *gt_ids, const int32_t *gt_count, const float *trk_boxes, const int32_t *trk_ids,
+                      const int32_t *trk_count, int n_seq, int n_frames, int cap, int n_gt_ids, int n_trk_ids, double thr, void *workspace,
+                      size_t workspace_bytes, int32_t *out_i, double *out_f, v2x_stream_t stream);
 
 /* ---------------------------------------------------------------- d: calibration probes (measurement)
  * No upstream counterpart.  The roofline fractions bench.py prints are graded against the datasheet peaks (8 TB/s, 2.5 PFLOP/s bf16);

@@ -6,9 +6,11 @@
 Both directories hold text files of lines `frame,id,x1,y1,w,h,...` (the track side is what track_codet.py writes; further columns are ignored).  Files
 are paired by their path relative to the directory; a file present on one side only is scored against an empty sequence, and the tool says so.  A
 sequence's frames are the numbers from the first to the last frame either file names (a frame neither names is an empty frame).
-One table row per file and one combined row: HOTA, DetA, AssA, DetRe, DetPr, AssRe, AssPr, LocA (v2x_sim_amd/utils/mot_metrics.py::Hota: all files
-in ONE library call) and MOTA, MOTP, IDSW (ClearMot, frame by frame); the combined row follows TrackEval's combination rules (counts add).
-`--out` writes the same record as JSON; main(argv) returns it.  At most 64 boxes per frame and side."""
+One table row per file and one combined row -- TrackEval's default metric set: HOTA, DetA, AssA, DetRe, DetPr, AssRe, AssPr, LocA
+(v2x_sim_amd/utils/mot_metrics.py::Hota: all files in ONE library call), MOTA, MOTP, IDSW, MT, ML, Frag (CLEAR) and IDF1, IDR, IDP (Identity), the last
+two families from `ClearIdentity`: all files in ONE more library call; the combined row follows TrackEval's combination rules (counts add).
+`--out` writes the same record as JSON, which additionally holds PT, the CLEAR and ID counts (TP, FN, FP, IDTP, IDFN, IDFP, MOTP_sum), MODA, sMOTA,
+CLR_Re, CLR_Pr and OWTA, HOTA(0), LocA(0), HOTALocA(0); main(argv) returns it.  At most 64 boxes per frame and side, 2048 ids per file and side."""
 import argparse
 import json
 import os
@@ -21,7 +23,8 @@ for _p in (ROOT, os.path.join(ROOT, "v2x-sim_amd")):
 
 import numpy as np  # noqa: E402
 
-COLUMNS = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA", "MOTA", "MOTP", "IDSW")
+COLUMNS = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA", "MOTA", "MOTP", "IDSW", "IDF1", "IDR", "IDP", "MT", "ML", "Frag")
+INT_COLUMNS = ("IDSW", "MT", "ML", "Frag")
 
 
 def read_mot(path):
@@ -58,10 +61,6 @@ def sequence_frames(gt, trk):
     return [gt.get(f, none) + trk.get(f, none) for f in range(min(numbers), max(numbers) + 1)]
 
 
-def _clear_row(tp, fp, fn, idsw, iou_sum):
-    return {"MOTA": (tp - fp - idsw) / (tp + fn) if tp + fn else 0.0, "MOTP": iou_sum / tp if tp else 0.0, "IDSW": idsw}
-
-
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gt", required=True, type=str, help="directory of ground-truth MOT-challenge text files")
@@ -69,7 +68,7 @@ def main(argv=None):
     ap.add_argument("--out", default="", type=str, help="write the record as JSON")
     args = ap.parse_args(argv)
     import torch
-    from v2x_sim_amd.utils.mot_metrics import HOTA_FIELDS, ClearMot, Hota
+    from v2x_sim_amd.utils.mot_metrics import HOTA_FIELDS, ClearIdentity, Hota, hota_extras
 
     if not torch.cuda.is_available():
         raise SystemExit("eval_track.py needs the MI355X: the hot path has no CPU fallback")
@@ -78,8 +77,7 @@ def main(argv=None):
     names = sorted(gt_files | trk_files)
     if not names:
         raise SystemExit("no .txt files under %s or %s" % (args.gt, args.trk))
-    hota, clear_rows, notes = Hota(), [], []
-    total = [0, 0, 0, 0, 0.0]
+    hota, clear, notes = Hota(), ClearIdentity(), []
     for name in names:
         note = "" if name in gt_files and name in trk_files else ("no tracker file: scored as an empty sequence" if name in gt_files
                                                                   else "no ground-truth file: scored as an empty sequence")
@@ -91,7 +89,6 @@ def main(argv=None):
         frames = sequence_frames(gt, trk)
         gb = torch.from_numpy(np.concatenate([f[1] for f in frames] + [np.zeros((0, 4), np.float32)])).to(device)      # one upload per side and file
         tb = torch.from_numpy(np.concatenate([f[3] for f in frames] + [np.zeros((0, 4), np.float32)])).to(device)
-        clear = ClearMot()
         g0 = t0 = 0
         for gi, gbox, ti, tbox in frames:
             g1, t1 = g0 + len(gi), t0 + len(ti)
@@ -99,25 +96,24 @@ def main(argv=None):
             clear.update(gb[g0:g1], gi, tb[t0:t1], ti)
             g0, t0 = g1, t1
         hota.new_sequence()
-        part = (clear.tp, clear.fp, clear.fn, clear.idsw, clear.iou_sum)
-        total = [a + b for a, b in zip(total, part)]
-        clear_rows.append(_clear_row(*part))
-    res = hota.result()
+        clear.new_sequence()
+    res, cres = hota.result(), clear.result()
 
     def row(name, h, c, note=""):
         r = {"name": name}
         r.update({k: h[k] for k in HOTA_FIELDS})
-        r.update(c)
+        r.update(hota_extras(h))
+        r.update({k: v for k, v in c.items() if k != "sequences"})
         if note:
             r["note"] = note
         return r
 
-    record = {"files": [row(n, h, c, note) for n, h, c, note in zip(names, res["sequences"], clear_rows, notes)],
-              "combined": row("COMBINED", res, _clear_row(*total))}
+    record = {"files": [row(n, h, c, note) for n, h, c, note in zip(names, res["sequences"], cres["sequences"], notes)],
+              "combined": row("COMBINED", res, cres)}
     width = max(len(n) for n in names + ["COMBINED"])
     print("%-*s " % (width, "file") + " ".join("%7s" % c for c in COLUMNS))
     for r in record["files"] + [record["combined"]]:
-        print("%-*s " % (width, r["name"]) + " ".join(("%7d" % r[c]) if c == "IDSW" else ("%7.4f" % r[c]) for c in COLUMNS))
+        print("%-*s " % (width, r["name"]) + " ".join(("%7d" % r[c]) if c in INT_COLUMNS else ("%7.4f" % r[c]) for c in COLUMNS))
     if args.out:
         with open(args.out, "w") as fh:
             json.dump(record, fh, indent=1)

@@ -14,8 +14,7 @@
 // formed from clamped counts and validated ids, so no input writes outside its buffers; a non-finite similarity or score reads as 0, so the assignment sees
 // finite numbers only (its termination: track_assign.h).  Duplicate ids within a frame (a caller error) make one of the two boxes win: unspecified, memory-safe.
 // Padding does not change a bit of a sequence's result: a padded frame, ground-truth id, track id or tile adds an exact 0.0 in the same place of the same order.
-#include "track_assign.h"
-#include <float.h>
+#include "track_sim.h"
 
 #define HOTA_MAX_ALPHA 32
 #define HOTA_NBUF 14
@@ -35,52 +34,6 @@ struct HotaWs {
     int32_t *nvg, *nvt;          // [S][F]            valid boxes of the frame
     int32_t *tpg;                // [S][n_alpha][NG]
 };
-
-__device__ __forceinline__ double hota_finite0(double v) { return fabs(v) <= DBL_MAX ? v : 0.0; }   // NaN and +-inf read as 0
-
-// ClearMot._iou64 on one pair: fp64 on the fp32 coordinates, operation by operation (no contraction: the host statement rounds every product)
-__device__ __forceinline__ double hota_iou(const float4 a, const float4 b) {
-#pragma clang fp contract(off)
-    const double w = fmax(0.0, fmin((double)a.z, (double)b.z) - fmax((double)a.x, (double)b.x));
-    const double h = fmax(0.0, fmin((double)a.w, (double)b.w) - fmax((double)a.y, (double)b.y));
-    const double wh = w * h;
-    const double aa = ((double)a.z - (double)a.x) * ((double)a.w - (double)a.y);
-    const double ab = ((double)b.z - (double)b.x) * ((double)b.w - (double)b.y);
-    return hota_finite0(wh / (aa + ab - wh));
-}
-
-__device__ __forceinline__ double hota_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ long long hota_wave_sum(long long v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// the slot of id g among the frame's ng compacted ground-truth ids (lowest slot if the caller repeated it), or -1; wave-uniform
-__device__ __forceinline__ int hota_slot_of(const int32_t *ids, int ng, int g, int lane) {
-    const int id = lane < ng ? ids[lane] : -1;
-    const unsigned long long b = __ballot(id == g);
-    return b ? __ffsll(b) - 1 : -1;
-}
-
-// compaction of one side of a frame: -> the number of valid boxes; boxes to LDS, ids to the workspace, both in slot order
-__device__ __forceinline__ int hota_compact(const float *boxes, const int32_t *ids, int count, int cap, int n_ids, float4 *box_lds, int32_t *ids_out, int lane) {
-    const int n = min(max(count, 0), cap);
-    const int id = lane < n ? ids[lane] : -1;
-    const bool ok = id >= 0 && id < n_ids;
-    const unsigned long long b = __ballot(ok);
-    if (ok) {
-        const int pos = __popcll(b & trk_lt_mask(lane));
-        box_lds[pos] = *reinterpret_cast<const float4 *>(boxes + (size_t)lane * 4);
-        ids_out[pos] = id;
-    }
-    return __popcll(b);
-}
 
 __global__ __launch_bounds__(TRK_N) void hota_sim_kernel(const float *gt_boxes, const int32_t *gt_ids, const int32_t *gt_count, const float *trk_boxes,
                                                          const int32_t *trk_ids, const int32_t *trk_count, const HotaDims d, const HotaWs w) {

@@ -163,6 +163,8 @@ SIGNATURES = {
                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "v2x_hota_workspace_size": (C.c_size_t, [C.c_int] * 6),
     "v2x_hota_sequences": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v2x_mot_workspace_size": (C.c_size_t, [C.c_int] * 5),
+    "v2x_mot_sequences": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "v2x_calib_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "v2x_calib_mfma": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "v2x_seg_argmax_confusion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

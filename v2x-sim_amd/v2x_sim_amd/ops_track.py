@@ -1,5 +1,5 @@
-"""Row f-5 (tracking): python wrappers over v2x_assign_iou and v2x_sort_step (csrc/track.hip) and v2x_hota_sequences (csrc/hota.hip).  Re-exported by
-ops.py (`ops.sort_step` ...)."""
+"""Row f-5 (tracking): python wrappers over v2x_assign_iou and v2x_sort_step (csrc/track.hip) v2x_hota_sequences (csrc/hota.hip) and v2x_mot_sequences (csrc/mot_seq.hip).
+Re-exported by ops.py (`ops.sort_step` ...)."""
 import ctypes as C
 
 import numpy as np
@@ -10,6 +10,8 @@ from ._launch import _dev, _stream
 
 TRACK_CAP = 64      # tracks per stream, detections read per map, rows / columns of a matrix: one wave
 HOTA_MAX_ALPHA = 32
+MOT_MAX_IDS = 2048  # ids per side of one sequence in mot_sequences: the assignment over the id space sits in one workgroup's LDS
+MOT_FIELDS_I = ("TP", "FN", "FP", "IDSW", "MT", "PT", "ML", "Frag", "IDTP", "IDFN", "IDFP")
 HOTA_ALPHAS = np.arange(0.05, 0.99, 0.05)      # TrackEval's 19 thresholds, numpy's exact float64 values
 
 
@@ -80,4 +82,35 @@ def hota_sequences(gt_boxes, gt_ids, gt_count, trk_boxes, trk_ids, trk_count, n_
                                       _dev(trk_count, torch.int32, "trk_count"), S, F, cap, int(n_gt_ids), int(n_trk_ids),
                                       _dev(alpha, torch.float64, "alpha"), n_alpha, _dev(ws, torch.uint8, "workspace"), nbytes,
                                       _dev(out_i, torch.int32, "out_i"), _dev(out_f, torch.float64, "out_f"), _stream()), "v2x_hota_sequences")
+    return out_i, out_f
+
+
+def mot_sequences(gt_boxes, gt_ids, gt_count, trk_boxes, trk_ids, trk_count, n_gt_ids, n_trk_ids, thr=0.5):
+    """The CLEAR MOT and Identity counts of S padded sequences in ONE library call (five launches, no host synchronisation).
+    The arguments of hota_sequences: gt_boxes (S, F, cap, 4) fp32 xyxy, gt_ids (S, F, cap) int32, gt_count (S, F) int32, the same for the tracks,
+    cap <= 64; ids per sequence in [0, n_gt_ids) / [0, n_trk_ids), both <= MOT_MAX_IDS; thr: the similarity threshold of both families.
+    -> out_i (S, 11) int32 = MOT_FIELDS_I (TP, FN, FP, IDSW, MT, PT, ML, Frag, IDTP, IDFN, IDFP); out_f (S, 1) float64 = the sum of the matched
+    similarities (MOTP = that sum / TP)."""
+    lib = _lib.load()
+    S, F, cap, four = gt_boxes.shape
+    if four != 4 or tuple(trk_boxes.shape) != (S, F, cap, 4):
+        raise ValueError("gt_boxes and trk_boxes must both be (S, F, cap, 4), got %s and %s" % (tuple(gt_boxes.shape), tuple(trk_boxes.shape)))
+    for name, t, shape in (("gt_ids", gt_ids, (S, F, cap)), ("trk_ids", trk_ids, (S, F, cap)), ("gt_count", gt_count, (S, F)), ("trk_count", trk_count, (S, F))):
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must be %s, got %s" % (name, shape, tuple(t.shape)))
+    if not np.isfinite(float(thr)):
+        raise ValueError("mot_sequences: thr = %r is not finite" % (thr,))
+    dev = gt_boxes.device
+    nbytes = lib.v2x_mot_workspace_size(S, F, cap, int(n_gt_ids), int(n_trk_ids))
+    if nbytes == 0:
+        raise ValueError("mot_sequences: S = %d, F = %d, cap = %d, n_gt_ids = %d, n_trk_ids = %d out of range (F >= 1, cap in [1, %d], ids per side in "
+                         "[0, %d])" % (S, F, cap, n_gt_ids, n_trk_ids, TRACK_CAP, MOT_MAX_IDS))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    out_i = torch.empty((S, len(MOT_FIELDS_I)), dtype=torch.int32, device=dev)
+    out_f = torch.empty((S, 1), dtype=torch.float64, device=dev)
+    _lib.check(lib.v2x_mot_sequences(_dev(gt_boxes, torch.float32, "gt_boxes"), _dev(gt_ids, torch.int32, "gt_ids"), _dev(gt_count, torch.int32, "gt_count"),
+                                     _dev(trk_boxes, torch.float32, "trk_boxes"), _dev(trk_ids, torch.int32, "trk_ids"),
+                                     _dev(trk_count, torch.int32, "trk_count"), S, F, cap, int(n_gt_ids), int(n_trk_ids), C.c_double(float(thr)),
+                                     _dev(ws, torch.uint8, "workspace"), nbytes, _dev(out_i, torch.int32, "out_i"), _dev(out_f, torch.float64, "out_f"),
+                                     _stream()), "v2x_mot_sequences")
     return out_i, out_f

@@ -11,7 +11,11 @@ wins > 1000).  They are fixed, their rows and columns zeroed, and the kernel ass
 
 The HOTA family (`Hota`; TrackEval's hota.py) is frame-independent once the global alignment score is known, so it is NOT scored
 frame by frame: `update` only collects, `result` pads every sequence to one shape and makes ONE `ops.hota_sequences` call (csrc/hota.hip, five launches)
-for all of them; what remains on the host is the arithmetic on 19 x 7 numbers per sequence."""
+for all of them; what remains on the host is the arithmetic on 19 x 7 numbers per sequence.  `hota_extras` adds OWTA and the `(0)` variants from that record.
+
+`ClearIdentity` scores CLEAR MOT (with MT / PT / ML / Frag) and the Identity family (IDF1, IDR, IDP) of whole sequences the same way: collect, pad (one padding
+for both classes), ONE `ops.mot_sequences` call (csrc/mot_seq.hip, five launches: the frames of a sequence are walked in order by one wave, the ID assignment
+over the sequence's id space by one workgroup).  `ClearMot` stays the online class for a tracker that is scored while it runs."""
 import numpy as np
 import torch
 
@@ -108,6 +112,55 @@ def _hota_fields(tp, fn, fp, loc, ass_a, ass_re, ass_pr, alphas):
     return out
 
 
+def _checked_frame(who, gt_boxes, gt_ids, trk_boxes, trk_ids):
+    """One frame as the collecting metrics (Hota, ClearIdentity) keep it: (gt_boxes float32 (G, 4) on the device, gt_ids list, trk_boxes, trk_ids)."""
+    if not gt_boxes.is_cuda or not trk_boxes.is_cuda:
+        raise RuntimeError("%s runs on the MI355X (cuda) device; the v2x_sim_amd hot path has no CPU fallback" % who)
+    gt_ids = [int(g) for g in (gt_ids.tolist() if torch.is_tensor(gt_ids) else gt_ids)]
+    trk_ids = [int(t) for t in (trk_ids.tolist() if torch.is_tensor(trk_ids) else trk_ids)]
+    cap = ops_track.TRACK_CAP
+    if len(gt_ids) > cap or len(trk_ids) > cap:
+        raise ValueError("%s takes at most %d ground-truth boxes and %d tracks per frame" % (who, cap, cap))
+    if len(set(gt_ids)) != len(gt_ids) or len(set(trk_ids)) != len(trk_ids):
+        raise ValueError("%s: an id occurs twice in one frame" % who)
+    return gt_boxes.reshape(len(gt_ids), 4).to(torch.float32), gt_ids, trk_boxes.reshape(len(trk_ids), 4).to(torch.float32), trk_ids
+
+
+def _pad_sequences(seqs):
+    """list (sequence) of lists of _checked_frame's frames -> every sequence padded to one shape, ids renumbered per sequence in order of first
+    appearance: (gt_boxes, gt_ids, gt_count, trk_boxes, trk_ids, trk_count, n_gt_ids, n_trk_ids), or None without a sequence."""
+    if not seqs:
+        return None
+    S = len(seqs)
+    F = max([len(q) for q in seqs] + [1])
+    cap = max([max(len(fr[1]), len(fr[3])) for q in seqs for fr in q] + [1])
+    ids = np.zeros((2, S, F, cap), dtype=np.int32)
+    count = np.zeros((2, S, F), dtype=np.int32)
+    n_ids = [0, 0]
+    boxes, dest = ([], []), ([], [])                    # per side: the frames' box tensors and their rows in the padded array
+    for s, q in enumerate(seqs):
+        remap = ({}, {})
+        for f, fr in enumerate(q):
+            for side in (0, 1):
+                b, i = fr[2 * side], fr[2 * side + 1]
+                n = len(i)
+                ids[side, s, f, :n] = [remap[side].setdefault(v, len(remap[side])) for v in i]
+                count[side, s, f] = n
+                if n:
+                    boxes[side].append(b)
+                    dest[side].append((s * F + f) * cap + np.arange(n))
+        n_ids = [max(n_ids[side], len(remap[side])) for side in (0, 1)]
+    dev = next((b[0].device for b in boxes if b), torch.device("cuda", torch.cuda.current_device()))
+    padded = []
+    for side in (0, 1):
+        p = torch.zeros((S * F * cap, 4), dtype=torch.float32, device=dev)
+        if boxes[side]:
+            p[torch.from_numpy(np.concatenate(dest[side])).to(dev)] = torch.cat(boxes[side])
+        padded.append(p.view(S, F, cap, 4))
+    ids_d, count_d = torch.from_numpy(ids).to(dev), torch.from_numpy(count).to(dev)
+    return padded[0], ids_d[0], count_d[0], padded[1], ids_d[1], count_d[1], n_ids[0], n_ids[1]
+
+
 class Hota(object):
     """update(gt_boxes (G, 4), gt_ids (G,), trk_boxes (T, 4), trk_ids (T,)) adds one frame to the current sequence (boxes x1, y1, x2, y2 on the device,
     read as float32; ids host integers of any value, unique within the frame; G, T <= 64), new_sequence() closes it.
@@ -121,16 +174,7 @@ class Hota(object):
         self._frames = []
 
     def update(self, gt_boxes, gt_ids, trk_boxes, trk_ids):
-        if not gt_boxes.is_cuda or not trk_boxes.is_cuda:
-            raise RuntimeError("Hota runs on the MI355X (cuda) device; the v2x_sim_amd hot path has no CPU fallback")
-        gt_ids = [int(g) for g in (gt_ids.tolist() if torch.is_tensor(gt_ids) else gt_ids)]
-        trk_ids = [int(t) for t in (trk_ids.tolist() if torch.is_tensor(trk_ids) else trk_ids)]
-        cap = ops_track.TRACK_CAP
-        if len(gt_ids) > cap or len(trk_ids) > cap:
-            raise ValueError("Hota takes at most %d ground-truth boxes and %d tracks per frame" % (cap, cap))
-        if len(set(gt_ids)) != len(gt_ids) or len(set(trk_ids)) != len(trk_ids):
-            raise ValueError("Hota: an id occurs twice in one frame")
-        self._frames.append((gt_boxes.reshape(len(gt_ids), 4).to(torch.float32), gt_ids, trk_boxes.reshape(len(trk_ids), 4).to(torch.float32), trk_ids))
+        self._frames.append(_checked_frame("Hota", gt_boxes, gt_ids, trk_boxes, trk_ids))
 
     def new_sequence(self):
         self._closed.append(self._frames)
@@ -139,37 +183,7 @@ class Hota(object):
     def padded(self):
         """Every sequence padded to one shape, ids renumbered per sequence in order of first appearance: the arguments of ops.hota_sequences --
         (gt_boxes, gt_ids, gt_count, trk_boxes, trk_ids, trk_count, n_gt_ids, n_trk_ids), or None without a sequence."""
-        seqs = self._closed + ([self._frames] if self._frames else [])
-        if not seqs:
-            return None
-        S = len(seqs)
-        F = max([len(q) for q in seqs] + [1])
-        cap = max([max(len(fr[1]), len(fr[3])) for q in seqs for fr in q] + [1])
-        ids = np.zeros((2, S, F, cap), dtype=np.int32)
-        count = np.zeros((2, S, F), dtype=np.int32)
-        n_ids = [0, 0]
-        boxes, dest = ([], []), ([], [])                    # per side: the frames' box tensors and their rows in the padded array
-        for s, q in enumerate(seqs):
-            remap = ({}, {})
-            for f, fr in enumerate(q):
-                for side in (0, 1):
-                    b, i = fr[2 * side], fr[2 * side + 1]
-                    n = len(i)
-                    ids[side, s, f, :n] = [remap[side].setdefault(v, len(remap[side])) for v in i]
-                    count[side, s, f] = n
-                    if n:
-                        boxes[side].append(b)
-                        dest[side].append((s * F + f) * cap + np.arange(n))
-            n_ids = [max(n_ids[side], len(remap[side])) for side in (0, 1)]
-        dev = next((b[0].device for b in boxes if b), torch.device("cuda", torch.cuda.current_device()))
-        padded = []
-        for side in (0, 1):
-            p = torch.zeros((S * F * cap, 4), dtype=torch.float32, device=dev)
-            if boxes[side]:
-                p[torch.from_numpy(np.concatenate(dest[side])).to(dev)] = torch.cat(boxes[side])
-            padded.append(p.view(S, F, cap, 4))
-        ids_d, count_d = torch.from_numpy(ids).to(dev), torch.from_numpy(count).to(dev)
-        return padded[0], ids_d[0], count_d[0], padded[1], ids_d[1], count_d[1], n_ids[0], n_ids[1]
+        return _pad_sequences(self._closed + ([self._frames] if self._frames else []))
 
     def result(self):
         args = self.padded()
@@ -186,4 +200,69 @@ class Hota(object):
         w = [(ass[..., k] * tp).sum(0) / tps for k in range(3)]
         out = _hota_fields(tp.sum(0), fn.sum(0), fp.sum(0), loc.sum(0), w[0], w[1], w[2], self.alphas)
         out["sequences"] = [_hota_fields(tp[s], fn[s], fp[s], loc[s], ass[s, :, 0], ass[s, :, 1], ass[s, :, 2], self.alphas) for s in range(S)]
+        return out
+
+
+def hota_extras(record):
+    """A Hota.result() record or one of its "sequences" -> TrackEval's remaining HOTA-family fields: OWTA = the mean over alpha of sqrt(DetRe AssA),
+    and HOTA(0), LocA(0), HOTALocA(0) = the first threshold's HOTA, LocA and their product."""
+    per = record["per_alpha"]
+    hota0, loc0 = float(per["HOTA"][0]), float(per["LocA"][0])
+    return {"OWTA": float(np.mean(np.sqrt(per["DetRe"] * per["AssA"]))), "HOTA(0)": hota0, "LocA(0)": loc0, "HOTALocA(0)": hota0 * loc0}
+
+
+CLEAR_ID_COUNTS = ops_track.MOT_FIELDS_I + ("MOTP_sum",)
+CLEAR_ID_FIELDS = ("MOTA", "MOTP", "MODA", "sMOTA", "CLR_Re", "CLR_Pr", "IDF1", "IDR", "IDP")
+
+
+def _clear_id_fields(c):
+    """The eleven counts and MOTP_sum of one sequence or of a combination -> the record with the ratios."""
+    tp, fn, fp, idsw, motp = c["TP"], c["FN"], c["FP"], c["IDSW"], c["MOTP_sum"]
+    idtp, idfn, idfp = c["IDTP"], c["IDFN"], c["IDFP"]
+    gt = max(1, tp + fn)
+    out = dict(c)
+    out.update({"MOTA": (tp - fp - idsw) / gt, "MOTP": motp / max(1, tp), "MODA": (tp - fp) / gt, "sMOTA": (motp - fp - idsw) / gt, "CLR_Re": tp / gt,
+                "CLR_Pr": tp / max(1, tp + fp), "IDR": idtp / max(1, idtp + idfn), "IDP": idtp / max(1, idtp + idfp),
+                "IDF1": idtp / max(1.0, idtp + 0.5 * idfp + 0.5 * idfn)})
+    return out
+
+
+class ClearIdentity(object):
+    """The CLEAR MOT family and the Identity family of whole sequences, batched: Hota's protocol.  update(gt_boxes (G, 4), gt_ids (G,), trk_boxes (T, 4),
+    trk_ids (T,)) adds one frame to the current sequence (boxes x1, y1, x2, y2 on the device, read as float32; ids host integers of any value, unique
+    within the frame; G, T <= 64), new_sequence() closes it.  result() pads (Hota's padding), makes ONE `ops.mot_sequences` call (csrc/mot_seq.hip, five
+    launches) and returns TP, FN, FP, IDSW, MT, PT, ML, Frag, IDTP, IDFN, IDFP, MOTP_sum, MOTA, MOTP, MODA, sMOTA, CLR_Re, CLR_Pr, IDF1, IDR, IDP of the
+    combination (every count and MOTP_sum add, the ratios are recomputed) and "sequences": the same record per sequence.
+    `ClearMot` remains the online class: one frame at a time, the same CLEAR reading."""
+
+    def __init__(self, threshold=0.5):
+        self.threshold = float(threshold)
+        self._closed = []
+        self._frames = []
+
+    def update(self, gt_boxes, gt_ids, trk_boxes, trk_ids):
+        self._frames.append(_checked_frame("ClearIdentity", gt_boxes, gt_ids, trk_boxes, trk_ids))
+
+    def new_sequence(self):
+        self._closed.append(self._frames)
+        self._frames = []
+
+    def padded(self):
+        """The arguments of ops.mot_sequences without thr (Hota.padded's tuple), or None without a sequence."""
+        return _pad_sequences(self._closed + ([self._frames] if self._frames else []))
+
+    def result(self):
+        args = self.padded()
+        seqs = []
+        if args is not None:
+            out_i, out_f = ops_track.mot_sequences(*args, thr=self.threshold)
+            out_i, out_f = out_i.cpu().numpy().astype(np.int64), out_f.cpu().numpy()
+            for s in range(out_i.shape[0]):
+                c = {k: int(out_i[s, j]) for j, k in enumerate(ops_track.MOT_FIELDS_I)}
+                c["MOTP_sum"] = float(out_f[s, 0])
+                seqs.append(c)
+        total = {k: sum(c[k] for c in seqs) for k in ops_track.MOT_FIELDS_I}
+        total["MOTP_sum"] = float(sum(c["MOTP_sum"] for c in seqs))
+        out = _clear_id_fields(total)
+        out["sequences"] = [_clear_id_fields(c) for c in seqs]
         return out
