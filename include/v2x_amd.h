@@ -403,6 +403,14 @@ int v2x_attn_handshake(const float *keys, const float *querys, const float *w_li
                        int Bt, int key_size, int query_size, int mode, float thres, float *prob, float *coef,
                        v2x_stream_t stream);
 
+/* The same launch with the normalisation over the keys chosen by `norm`: 0 = softmax (v2x_attn_handshake's bits), 1 = sparsemax
+ * (When2com(sparse=True)): per query, with the scores z sorted descending, k* = max{ j : 1 + j z_(j) > sum_{i<=j} z_(i) },
+ * tau = (sum_{i<=k*} z_(i) - 1) / k*, prob_k = max(z_k - tau, 0) -- the projection of the score column onto the simplex, exact zeros
+ * outside its support.  The selections act on prob as above (the first maximum wins 'argmax_test').  Any other norm: V2X_EINVAL. */
+int v2x_attn_handshake_norm(const float *keys, const float *querys, const float *w_lin, const float *b_lin, int A,
+                            int Bt, int key_size, int query_size, int mode, int norm, float thres, float *prob,
+                            float *coef, v2x_stream_t stream);
+
 /* ---------------------------------------------------------------- a8: seg argmax + confusion matrix
  * logits fp32 NHWC [n][H][W][n_cls]; label uint8 [n][H][W]; pred uint8 [n][H][W] (may be NULL);
  * conf int64 [n_cls][n_cls] (rows = label, cols = prediction), accumulated (caller zeroes). */

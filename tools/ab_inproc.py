@@ -19,7 +19,10 @@ from v2x_sim_amd import _lib, ops, packing  # noqa: E402
 def load_variant(path):
     lib = C.CDLL(path)
     for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:              # a build of an earlier commit lacks the entries added since (the ABI is additive): its cases skip them
+            continue
         fn.restype, fn.argtypes = res, args
     assert lib.v2x_abi_version() == _lib.ABI_VERSION
     return lib
@@ -62,11 +65,55 @@ def main():
              ("halo heads: 32 -> 64 -> 12 | 36 fp32 @256", 32, 0, 64, 256, 0, "heads"),
              ("s2 conv2_1: 64 -> 128 @128 -> 64", 64, 0, 128, 128, 0, "s2"), ("s2 conv3_1: 128 -> 256 @64 -> 32", 128, 0, 256, 64, 0, "s2"),
              ("s2 conv4_1: 256 -> 512 @32 -> 16", 256, 0, 512, 32, 0, "s2"), ("pair conv_pre_1 -> conv_pre_2 from the bit grid @256", 32, 0, 32, 256, 0, "pair")]
+    cases.append(("attn handshake: A = 5, Bt = 64, K = 1024, Q = 32", 0, 0, 0, 0, 0, "attn"))
     if only:
         cases = [c for c in cases if only in c[0]]
     n = 320
     for name, c0, c1, cout, hw, up, gru in cases:
         split = 0
+        if gru == "attn":
+            # the when2com handshake through the entry every build has (softmax, norm = 0); then, per variant that has v2x_attn_handshake_norm,
+            # the sparsemax form next to it (no pairing: information only)
+            A, Bt = 5, 64
+            keys = (torch.randn(A * Bt, 1024, generator=g) * 0.3).to(dev)
+            querys = torch.randn(A * Bt, 32, generator=g).to(dev)
+            wl, bl = (torch.randn(1024, 32, generator=g) * 0.05).to(dev), (torch.randn(1024, generator=g) * 0.05).to(dev)
+            outs = []
+            for v in (0, 1):
+                use(v)
+                outs.append(ops.attn_handshake(keys, querys, wl, bl, A, Bt, "activated")[1].clone())
+            same = torch.equal(outs[0], outs[1])
+            reps = 200
+            t = np.zeros((reps, 2))
+            for r in range(-5, reps):
+                for v in ((0, 1) if r % 2 == 0 else (1, 0)):
+                    use(v)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    ops.attn_handshake(keys, querys, wl, bl, A, Bt, "activated")
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if r >= 0:
+                        t[r, v] = e0.elapsed_time(e1) * 1e3
+            d = t[:, 1] - t[:, 0]
+            print("%-44s A %.1f us  B %.1f us  B-A %+.1f us (%+.2f %%, s.e. %.2f %%)  outputs %s" % (
+                name, t[:, 0].mean(), t[:, 1].mean(), d.mean(), 100 * d.mean() / t[:, 0].mean(), 100 * d.std() / np.sqrt(reps) / t[:, 0].mean(),
+                "bit-identical" if same else "DIFFER"))
+            for v in (0, 1):
+                if not hasattr(libs[v], "v2x_attn_handshake_norm"):
+                    continue
+                use(v)
+                ts = []
+                for r in range(-5, reps):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    ops.attn_handshake(keys, querys, wl, bl, A, Bt, "activated", norm="sparsemax")
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if r >= 0:
+                        ts.append(e0.elapsed_time(e1) * 1e3)
+                print("%-44s %s sparsemax (norm = 1) %.1f us" % (name, "AB"[v], float(np.mean(ts))))
+            continue
         if gru == "pair":
             pa = packing.pack_conv_halo(name + ".a", torch.randn(32, 32, 3, 3, generator=g) * 0.05, torch.rand(32, generator=g) + 0.5, torch.randn(32, generator=g) * 0.1, relu=True, device=dev)
             pb = packing.pack_conv_halo(name + ".b", torch.randn(32, 32, 3, 3, generator=g) * 0.05, torch.rand(32, generator=g) + 0.5, torch.randn(32, generator=g) * 0.1, relu=True, device=dev)

@@ -4,9 +4,10 @@
 
     python tools/seg/train_seg.py --data synthetic --com v2v --steps 300 --batch 2 --logpath out/
     python tools/seg/train_seg.py --data /path/V2X-Sim-seg/train --com v2v --nepoch 5 --batch 2 --logpath out/
+    python tools/seg/train_seg.py --data synthetic --com when2com --steps 20 --batch 1        (--com: every detection baseline but `late`)
 
 Synthetic scenes (utils/synthetic_scene.py: vehicle footprints as class 1), PyTorch-ROCm autograd over the HIP engine's
-parameter tree, checkpoint with upstream's 'model_state_dict' key for tools/seg/test_seg.py --resume."""
+parameter tree, checkpoint with upstream's 'model_state_dict' key for tools/seg/test_seg.py / eval_seg.py --resume."""
 import argparse
 import os
 import sys
@@ -33,7 +34,9 @@ def seg_batch(config, frames, agents, seed, device, grid):
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("-d", "--data", default="synthetic", type=str)
-    ap.add_argument("--com", default="v2v", choices=["lowerbound", "upperbound", "v2v"])
+    ap.add_argument("--com", default="v2v", choices=["lowerbound", "upperbound", "v2v", "when2com", "who2com", "sum", "mean", "max", "cat", "disco"])
+    ap.add_argument("--inference", default=None, choices=["softmax", "activated", "argmax_test"],
+                    help="when2com / who2com: the selection of the communication rate printed after each epoch (training itself uses the soft scores)")
     ap.add_argument("--batch", default=2, type=int)
     ap.add_argument("--steps", default=300, type=int)
     ap.add_argument("--nepoch", default=1, type=int)
@@ -65,7 +68,7 @@ def main(argv=None):
     class_weight = [float(v) for v in args.class_weight.split(",")] if args.class_weight else None
     from v2x_sim_amd import ops
     from v2x_sim_amd.configs import Config
-    from v2x_sim_amd.models.seg import FaFNetSeg, V2VNetSeg
+    from v2x_sim_amd.models.seg import COM_CLASSES, When2comSeg, default_inference
     from v2x_sim_amd.train.loop import init_for_training
     from v2x_sim_amd.utils import comm
     from v2x_sim_amd.utils.SegModule import SegModule
@@ -74,8 +77,10 @@ def main(argv=None):
     device = torch.device("cuda:0")
     config = Config("train", binary=True, only_det=True)
     A = args.num_agent
-    ckw = comm.model_kwargs(args, intermediate=args.com == "v2v")
-    model = V2VNetSeg(config, num_agent=A, **ckw) if args.com == "v2v" else FaFNetSeg(config, num_agent=A)
+    ckw = comm.model_kwargs(args, intermediate=args.com not in ("lowerbound", "upperbound"))
+    model = COM_CLASSES[args.com](config, num_agent=A, **ckw)
+    if args.engine == "hip-graph" and args.com not in ("lowerbound", "upperbound", "v2v"):
+        print("--engine hip-graph: no captured step exists for --com %s, its steps run eager (the kernel loss paths stay on)" % args.com, file=sys.stderr)
     ckpt = None
     if args.resume:
         ckpt = torch.load(args.resume, map_location="cpu")
@@ -110,16 +115,22 @@ def main(argv=None):
     module = SegModule(model, None, config, opt, 0, class_weight=class_weight)
     grid = ops.VoxelGrid(config.voxel_size, config.area_extents)
     for epoch in range(start, args.nepoch + 1):
-        losses = []
+        losses, last = [], None
         if loader is not None:
             for samples in loader:
-                losses.append(module.step(seg_batch_on_device(samples, grid, device), len(samples[0]), len(samples)))
+                last = (seg_batch_on_device(samples, grid, device), len(samples))
+                losses.append(module.step(last[0], len(samples[0]), len(samples)))
         else:
             for it in range(args.steps):
-                losses.append(module.step(seg_batch(config, args.batch, A, (args.seed + epoch) * 1000003 + it, device, grid), A, args.batch))
+                last = (seg_batch(config, args.batch, A, (args.seed + epoch) * 1000003 + it, device, grid), args.batch)
+                losses.append(module.step(last[0], A, args.batch))
                 if args.log and it % 20 == 0:
                     print("step %4d  loss %.4f" % (it, losses[-1]), flush=True)
         print("epoch %d: mean loss of the last 20 steps %.4f" % (epoch, float(np.mean(losses[-20:]))))
+        if isinstance(model, When2comSeg) and last is not None:
+            # the communication rate of the current weights on the epoch's last batch, synthetic or parsed (off-diagonal non-zero links per agent and frame)
+            module.predict(last[0], batch_size=last[1], inference=args.inference or default_inference(args.com))
+            print("epoch %d: communication rate %.3f" % (epoch, module.last_num_connect))
         if args.logpath:
             os.makedirs(args.logpath, exist_ok=True)
             torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": opt.state_dict(),

@@ -7,7 +7,7 @@
 // include/v2x_amd.h.  The whole handshake of a frame is a 5x5 problem with 1024-long dot
 // products: one workgroup per frame, projected queries kept in LDS, one wave per
 // (key, query) pair with a 64-lane shuffle reduction, softmax over <= 32 keys by a single
-// thread per query.  fp32 throughout.
+// thread per query -- or, norm = 1 (When2com(sparse=True), v2x_attn_handshake_norm), sparsemax.  fp32 throughout.
 #include "common.h"
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void attn_handshake_kernel(const float *__rest
                                                              const float *__restrict__ querys,
                                                              const float *__restrict__ w_lin,
                                                              const float *__restrict__ b_lin, int A, int Bt,
-                                                             int key_size, int query_size, int mode, float thres,
+                                                             int key_size, int query_size, int mode, int norm, float thres,
                                                              float *__restrict__ prob, float *__restrict__ coef) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float *qp = reinterpret_cast<float *>(smem_raw);  // [A][key_size] projected queries
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void attn_handshake_kernel(const float *__rest
     }
     __syncthreads();
     // 3. softmax over keys k for every query q, then the selection
-    if (threadIdx.x < A) {
+    if (norm == 0 && threadIdx.x < A) {
         const int q = threadIdx.x;
         float mx = -INFINITY;
         for (int k = 0; k < A; ++k) mx = fmaxf(mx, sc[k * A + q]);
@@ -102,20 +102,83 @@ __global__ __launch_bounds__(256) void attn_handshake_kernel(const float *__rest
             coef[((size_t)f * A + k) * A + q] = c;
         }
     }
+    // 3'. norm = 1 (a uniform branch): sparsemax over the keys (Martins & Astudillo 2016) -- the Euclidean projection of the score column onto
+    // the simplex -- then the same selections on p.  z_k = score - column maximum (sparsemax is shift-invariant: with scores of 1e3 the sums
+    // below then cancel at the size of the gaps, not of the scores); a copy of the column is sorted descending in LDS (srt: A*A floats after
+    // qs, column q = srt[j * A + q], one thread per column -- insertion sort, A <= 32; a private array indexed by j would live in scratch);
+    // k* = max{ j : 1 + j z_(j) > sum_{i <= j} z_(i) } with the sum taken in the sorted order, tau = (sum_{i <= k*} z_(i) - 1) / k*,
+    // p_k = max(z_k - tau, 0).  j = 1 always holds (1 + z_(1) > z_(1)), so k* >= 1.
+    if (norm != 0 && threadIdx.x < A) {
+        const int q = threadIdx.x;
+        float *srt = qs + A * query_size;
+        float mx = -INFINITY;
+        for (int k = 0; k < A; ++k) mx = fmaxf(mx, sc[k * A + q]);
+        for (int k = 0; k < A; ++k) {
+            const float v = sc[k * A + q] - mx;
+            int j = k;
+            while (j > 0 && srt[(j - 1) * A + q] < v) {
+                srt[j * A + q] = srt[(j - 1) * A + q];
+                --j;
+            }
+            srt[j * A + q] = v;
+        }
+        float cum = 0.f, csum = 0.f;
+        int kstar = 1;
+        for (int j = 1; j <= A; ++j) {
+            const float zj = srt[(j - 1) * A + q];
+            cum += zj;
+            if (1.f + (float)j * zj > cum) {
+                kstar = j;
+                csum = cum;
+            }
+        }
+        const float tau = (csum - 1.f) / (float)kstar;
+        int arg = 0;
+        float best = -INFINITY;
+        for (int k = 0; k < A; ++k) {
+            const float p = fmaxf(sc[k * A + q] - mx - tau, 0.f);
+            prob[((size_t)f * A + k) * A + q] = p;
+            if (p > best) {  // first maximum wins, as torch.max
+                best = p;
+                arg = k;
+            }
+        }
+        for (int k = 0; k < A; ++k) {
+            const float p = fmaxf(sc[k * A + q] - mx - tau, 0.f);
+            float c;
+            if (mode == 0) c = p;
+            else if (mode == 1) c = (p > thres) ? p : 0.f;
+            else c = (k == arg) ? 1.f : 0.f;
+            coef[((size_t)f * A + k) * A + q] = c;
+        }
+    }
+}
+
+static int attn_handshake_launch(const float *keys, const float *querys, const float *w_lin, const float *b_lin, int A, int Bt, int key_size,
+                                 int query_size, int mode, int norm, float thres, float *prob, float *coef, v2x_stream_t stream) {
+    V2X_REQUIRE(keys && querys && w_lin && b_lin && prob && coef, "v2x_attn_handshake: null pointer");
+    V2X_REQUIRE(A > 0 && A <= 32 && Bt > 0 && key_size > 0 && query_size > 0, "v2x_attn_handshake: bad dims");
+    V2X_REQUIRE(mode >= 0 && mode <= 2, "v2x_attn_handshake: mode must be 0 (softmax), 1 (activated) or 2 (argmax_test)");
+    V2X_REQUIRE(norm == 0 || norm == 1, "v2x_attn_handshake_norm: norm must be 0 (softmax) or 1 (sparsemax)");
+    // norm = 1: another A*A floats after qs, the sorted copy of every score column
+    const size_t smem = ((size_t)A * key_size + (size_t)A * A + (size_t)A * query_size + (norm ? (size_t)A * A : 0)) * sizeof(float);
+    V2X_REQUIRE(smem <= 64 * 1024, "v2x_attn_handshake: A*key_size too large for LDS staging");
+    hipLaunchKernelGGL(attn_handshake_kernel, dim3(Bt), dim3(256), smem, (hipStream_t)stream, keys, querys, w_lin,
+                       b_lin, A, Bt, key_size, query_size, mode, norm, thres, prob, coef);
+    V2X_CHECK_LAUNCH("attn_handshake_kernel");
+    return V2X_OK;
 }
 
 extern "C" int v2x_attn_handshake(const float *keys, const float *querys, const float *w_lin, const float *b_lin,
                                   int A, int Bt, int key_size, int query_size, int mode, float thres, float *prob,
                                   float *coef, v2x_stream_t stream) {
-    V2X_REQUIRE(keys && querys && w_lin && b_lin && prob && coef, "v2x_attn_handshake: null pointer");
-    V2X_REQUIRE(A > 0 && A <= 32 && Bt > 0 && key_size > 0 && query_size > 0, "v2x_attn_handshake: bad dims");
-    V2X_REQUIRE(mode >= 0 && mode <= 2, "v2x_attn_handshake: mode must be 0 (softmax), 1 (activated) or 2 (argmax_test)");
-    const size_t smem = ((size_t)A * key_size + (size_t)A * A + (size_t)A * query_size) * sizeof(float);
-    V2X_REQUIRE(smem <= 64 * 1024, "v2x_attn_handshake: A*key_size too large for LDS staging");
-    hipLaunchKernelGGL(attn_handshake_kernel, dim3(Bt), dim3(256), smem, (hipStream_t)stream, keys, querys, w_lin,
-                       b_lin, A, Bt, key_size, query_size, mode, thres, prob, coef);
-    V2X_CHECK_LAUNCH("attn_handshake_kernel");
-    return V2X_OK;
+    return attn_handshake_launch(keys, querys, w_lin, b_lin, A, Bt, key_size, query_size, mode, 0, thres, prob, coef, stream);
+}
+
+extern "C" int v2x_attn_handshake_norm(const float *keys, const float *querys, const float *w_lin, const float *b_lin,
+                                       int A, int Bt, int key_size, int query_size, int mode, int norm, float thres, float *prob,
+                                       float *coef, v2x_stream_t stream) {
+    return attn_handshake_launch(keys, querys, w_lin, b_lin, A, Bt, key_size, query_size, mode, norm, thres, prob, coef, stream);
 }
 
 // ---- a8: per-pixel argmax over class logits + LDS-binned integer confusion matrix ----------

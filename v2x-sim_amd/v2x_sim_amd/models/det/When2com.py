@@ -1,7 +1,7 @@
 """when2com / who2com -- mirror of upstream coperception/models/det/When2com.py (absent from
 /root/reference; README.md:101 names both benchmarks).  A policy tower (its own LidarEncoder
 + 5 convs) feeds two MLPs producing a 1024-d key and a 32-d query per agent; scores =
-key . Linear(query), softmax over the keys; at inference 'activated' keeps weights > 0.2
+key . Linear(query), softmax over the keys (sparse=True: sparsemax, exact zeros outside its support); at inference 'activated' keeps weights > 0.2
 (when2com), 'argmax_test' keeps the top-1 key (who2com); the fused map of agent q is
 sum_k coef[k, q] * warp(F_k -> q).
 
@@ -115,8 +115,6 @@ class When2com(IntermediateModelBase):
         if self.only_v2i:
             raise NotImplementedError("when2com under a link mask (only_v2i) is out of scope: its attention has no agreed reading "
                                       "under a mask (DESIGN.md section 9)")
-        if sparse:
-            raise NotImplementedError("sparsemax attention is out of scope (DESIGN.md section 8)")
         if not has_query:
             raise NotImplementedError("has_query=False is out of scope")
         # the two open readings of oracle/ASSUMPTIONS.md as switches (defaults = the first reading): row 30 attn_index "kq" -- fused[q] =
@@ -125,7 +123,7 @@ class When2com(IntermediateModelBase):
         if attn_index not in ("kq", "qk"):
             raise ValueError("attn_index must be 'kq' or 'qk'")
         self.attn_index, self.renormalize = attn_index, bool(renormalize)
-        self.sparse = sparse
+        self.sparse = bool(sparse)            # sparsemax instead of softmax over the keys: exact zeros outside the support
         self.warp_flag = warp_flag
         self.key_size, self.query_size = key_size, query_size
         self.query_key_net = PolicyNet4(in_channels=in_channels)
@@ -178,12 +176,15 @@ class When2com(IntermediateModelBase):
         for layer in pk["tower"]["convs"]:
             y = ops.run_layer(layer, y)
         keys, querys = KmGenerator.run_pair(pk["keyquery"], y)     # (the separate MLPs pk["key"], pk["query"] give the same bits: tests)
-        return ops.attn_handshake(keys, querys, pk["w_lin"], pk["b_lin"], self.agent_num, batch_size, mode)
+        return ops.attn_handshake(keys, querys, pk["w_lin"], pk["b_lin"], self.agent_num, batch_size, mode, norm=self.attn_norm)
 
-    @ops.latency_entry
-    def forward_nhwc(self, x0, trans_matrices, num_agent_tensor, training=True, inference="activated",
-                     batch_size=1, plan=None):
-        pk = self.packed(x0.device)
+    @property
+    def attn_norm(self):
+        return "sparsemax" if self.sparse else "softmax"
+
+    def fused_feats(self, pk, x0, trans_matrices, num_agent_tensor, training, inference, batch_size, plan):
+        """Encoder, handshake and the weighted warp-sum: -> (the pyramid with the fused map at self.layer, prob, coef).  What the detection
+        model and its segmentation variant (models/seg: When2comSeg) share; each decodes the pyramid with its own heads."""
         A = self.agent_num
         feats = LidarEncoder.run(pk["enc"], x0)
         if plan is None:
@@ -210,6 +211,13 @@ class When2com(IntermediateModelBase):
             fused = torch.zeros_like(feat)
             fused.index_copy_(0, plan["rows"], fused_items)
         feats[self.layer] = fused
+        return feats, prob, coef
+
+    @ops.latency_entry
+    def forward_nhwc(self, x0, trans_matrices, num_agent_tensor, training=True, inference="activated",
+                     batch_size=1, plan=None):
+        pk = self.packed(x0.device)
+        feats, prob, coef = self.fused_feats(pk, x0, trans_matrices, num_agent_tensor, training, inference, batch_size, plan)
         res = self.decode_heads(pk, feats)
         res["prob_action"] = prob
         res["coef"] = coef

@@ -4,6 +4,9 @@ Upstream coperception/models/seg/* is not in /root/reference and its backbone wi
 unverified, so the build-owned spec reuses the detection backbone (rows a2/a6)
 and replaces the det heads by a 1x1 conv 32 -> n_classes producing NHWC fp32 logits
 (DESIGN.md section 3.6).  n_classes = 8 as recollected for V2X-Sim.
+
+Every --com of detection except `late` has its class here: the detection twin plus `outc`, the twin's forward up to the fused pyramid, then
+_seg_tail (decoder + class head) in place of the detection heads.
 """
 import torch.nn as nn
 
@@ -11,7 +14,9 @@ from ... import ops, packing, tuning
 from ..._lib import V2X_EPI_F32
 from ..det.base import LidarDecoder, LidarEncoder, _ParamsOnly
 from ..det.FaFNet import FaFNet
+from ..det.fusion import CatFusion, DiscoNet, MaxFusion, MeanFusion, SumFusion
 from ..det.V2VNet import V2VNet
+from ..det.When2com import When2com
 
 
 class OutConv(_ParamsOnly):
@@ -95,3 +100,85 @@ class FaFNetSeg(FaFNet):
         pk = self.packed(x0.device)
         feats = LidarEncoder.run(pk["enc"], x0, zbits=zbits)
         return _seg_tail(pk, feats)
+
+
+class When2comSeg(When2com):
+    """when2com / who2com with the class head: the handshake and the weighted warp-sum of the detection model (When2com.fused_feats), then
+    decoder + 1x1 head.  Every constructor switch of When2com, `sparse` (sparsemax) included; a link mask raises as there."""
+
+    def __init__(self, config, n_classes=8, **kw):
+        super().__init__(config, **kw)
+        self.n_classes = n_classes
+        self.outc = OutConv(32, n_classes)
+
+    def _pack(self, device):
+        pk = super()._pack(device)
+        pk["seg"] = _pack_seg_head(self.outc, device)
+        pk["seg_fused"] = _pack_seg_fused(self.decoder, self.outc, device)
+        return pk
+
+    @ops.latency_entry
+    def forward_nhwc(self, x0, trans_matrices, num_agent_tensor, training=True, inference="activated", batch_size=1, plan=None,
+                     return_handshake=False):
+        """-> logits (A*B, X, Y, n_classes) fp32 NHWC; return_handshake=True: (logits, prob, coef), the two (B, A_key, A_query)."""
+        pk = self.packed(x0.device)
+        feats, prob, coef = self.fused_feats(pk, x0, trans_matrices, num_agent_tensor, training, inference, batch_size, plan)
+        logits = _seg_tail(pk, feats)
+        return (logits, prob, coef) if return_handshake else logits
+
+    def forward(self, bevs, trans_matrices, num_agent_tensor, training=True, inference="activated", batch_size=1):
+        return self.forward_nhwc(self._input_nhwc(bevs), trans_matrices, num_agent_tensor, training, inference, batch_size)
+
+
+class _FusionSegMixin(object):
+    """The class head on a FusionBase model: FusionBase.forward_nhwc with _seg_tail in place of decode_heads.  Link masks and compress_level are
+    the twin's (make_plan / the encoder's codec); the bit-grid input (zbits) is not taken, as in the twins."""
+
+    def __init__(self, config, n_classes=8, **kw):
+        super().__init__(config, **kw)
+        self.n_classes = n_classes
+        self.outc = OutConv(32, n_classes)
+
+    def _pack(self, device):
+        pk = super()._pack(device)
+        pk["seg"] = _pack_seg_head(self.outc, device)
+        pk["seg_fused"] = _pack_seg_fused(self.decoder, self.outc, device)
+        return pk
+
+    @ops.latency_entry
+    def forward_nhwc(self, x0, trans_matrices, num_agent_tensor, batch_size=1, plan=None):
+        pk = self.packed(x0.device)
+        feats = LidarEncoder.run(pk["enc"], x0)
+        if plan is None:
+            plan = self.make_plan(num_agent_tensor, batch_size, x0.device)
+        feats[self.layer] = self.fuse(feats[self.layer], trans_matrices, plan, batch_size, pk)
+        return _seg_tail(pk, feats)
+
+
+class SumFusionSeg(_FusionSegMixin, SumFusion):
+    pass
+
+
+class MeanFusionSeg(_FusionSegMixin, MeanFusion):
+    pass
+
+
+class MaxFusionSeg(_FusionSegMixin, MaxFusion):
+    pass
+
+
+class CatFusionSeg(_FusionSegMixin, CatFusion):
+    pass
+
+
+class DiscoNetSeg(_FusionSegMixin, DiscoNet):
+    pass
+
+
+# --com of tools/seg/train_seg.py and eval_seg.py -> the class (who2com is a When2comSeg evaluated with inference 'argmax_test', as in tools/det/test_codet.py)
+COM_CLASSES = {"lowerbound": FaFNetSeg, "upperbound": FaFNetSeg, "v2v": V2VNetSeg, "when2com": When2comSeg, "who2com": When2comSeg,
+               "sum": SumFusionSeg, "mean": MeanFusionSeg, "max": MaxFusionSeg, "cat": CatFusionSeg, "disco": DiscoNetSeg}
+
+
+def default_inference(com):
+    return "argmax_test" if com == "who2com" else "activated"

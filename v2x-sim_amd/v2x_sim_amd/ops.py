@@ -517,12 +517,22 @@ def _warp_frame_order(items, A, Bt):
 ATTN_MODES = {"softmax": 0, "activated": 1, "argmax_test": 2}
 
 
-def attn_handshake(keys, querys, w_lin, b_lin, A, Bt, mode, thres=0.2):
-    """keys (A*Bt, K) fp32, querys (A*Bt, Q) fp32 -> prob, coef (Bt, A_key, A_query) fp32."""
+ATTN_NORMS = {"softmax": 0, "sparsemax": 1}
+
+
+def attn_handshake(keys, querys, w_lin, b_lin, A, Bt, mode, thres=0.2, norm="softmax"):
+    """keys (A*Bt, K) fp32, querys (A*Bt, Q) fp32 -> prob, coef (Bt, A_key, A_query) fp32.  norm: how the scores of a query are
+    normalised over the keys -- "softmax", or "sparsemax" (When2com(sparse=True): exact zeros outside the support)."""
     lib = _lib.load()
     K, Q = keys.shape[1], querys.shape[1]
     prob = torch.empty((Bt, A, A), dtype=torch.float32, device=keys.device)
     coef = torch.empty_like(prob)
+    if ATTN_NORMS[norm] != 0:
+        _lib.check(lib.v2x_attn_handshake_norm(_dev(keys, torch.float32, "keys"), _dev(querys, torch.float32, "querys"),
+                                               _dev(w_lin, torch.float32, "w_lin"), _dev(b_lin, torch.float32, "b_lin"), A, Bt,
+                                               K, Q, ATTN_MODES[mode], ATTN_NORMS[norm], C.c_float(thres), _dev(prob, torch.float32, "prob"),
+                                               _dev(coef, torch.float32, "coef"), _stream()), "v2x_attn_handshake_norm")
+        return prob, coef
     _lib.check(lib.v2x_attn_handshake(_dev(keys, torch.float32, "keys"), _dev(querys, torch.float32, "querys"),
                                       _dev(w_lin, torch.float32, "w_lin"), _dev(b_lin, torch.float32, "b_lin"), A, Bt,
                                       K, Q, ATTN_MODES[mode], C.c_float(thres), _dev(prob, torch.float32, "prob"),

@@ -347,7 +347,7 @@ class ShardedWhen2com:
         keys = self.exchange(k_loc)                                # (A*Bt, 1024) on every rank
         querys = self.exchange(q_loc)                              # (A*Bt, 32)
         mode = "softmax" if (training or inference == "softmax") else inference
-        prob, coef = ops.attn_handshake(keys, querys, pk["w_lin"], pk["b_lin"], sh.A, sh.Bt, mode)
+        prob, coef = ops.attn_handshake(keys, querys, pk["w_lin"], pk["b_lin"], sh.A, sh.Bt, mode, norm=getattr(m, "attn_norm", "softmax"))
         if getattr(m, "renormalize", False) and mode == "activated":          # the second readings of ASSUMPTIONS rows 31 / 30, as in When2com.forward_nhwc
             coef = m.renormalized(coef)
         transposed = getattr(m, "attn_index", "kq") == "qk"

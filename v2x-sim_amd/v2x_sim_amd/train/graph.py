@@ -216,9 +216,24 @@ def v2v_fuse(model, feat, trans, num_agent_tensor, B, gru_conv=None):
     return cur
 
 
+def sparsemax(z, dim):
+    """Sparsemax along `dim` (Martins & Astudillo 2016): with the entries sorted descending, k* = max{ j : 1 + j z_(j) >
+    sum_{i<=j} z_(i) }, tau = (sum_{i<=k*} z_(i) - 1) / k*, p = max(z - tau, 0).  Differentiable: the gradient flows through the sorted
+    values and the clamp (inside the support dp_k / dz_l = [k = l] - 1 / k*, outside 0)."""
+    z = z - z.max(dim=dim, keepdim=True).values.detach()          # shift-invariant; keeps the cumulative sums at the size of the gaps
+    srt = z.sort(dim=dim, descending=True).values
+    cum = srt.cumsum(dim)
+    shape = [1] * z.dim()
+    shape[dim] = -1
+    j = torch.arange(1, z.shape[dim] + 1, device=z.device, dtype=z.dtype).view(shape)
+    kstar = (1 + j * srt > cum).to(z.dtype).sum(dim=dim, keepdim=True)      # the condition holds on a prefix: its length is the maximum
+    tau = (cum.gather(dim, kstar.long() - 1) - 1) / kstar
+    return (z - tau).clamp(min=0)
+
+
 def when2com_fuse(model, x, feat, trans, num_agent_tensor, B, training=True, inference="softmax"):
     """when2com / who2com fusion (upstream When2com.py): policy tower -> key / query MLPs -> scores = key . Linear(query),
-    softmax over the keys; training uses the soft scores, inference 'activated' / 'argmax_test' as the HIP path.
+    softmax over the keys (model.sparse: sparsemax); training uses the soft scores, inference 'activated' / 'argmax_test' as the HIP path.
     x (A*B, Z, X, Y) input, feat (A*B, C, H, W) fusion-layer maps -> fused maps (zeros for padding agents)."""
     A = model.agent_num
     if _links(model, B) is not None:
@@ -232,7 +247,8 @@ def when2com_fuse(model, x, feat, trans, num_agent_tensor, B, training=True, inf
     keys, querys = model.key_net.fc(flat), model.query_net.fc(flat)
     key_mat = torch.stack([keys[B * i:B * (i + 1)] for i in range(A)], 1)       # (B, A, K)
     query_mat = torch.stack([querys[B * i:B * (i + 1)] for i in range(A)], 1)   # (B, A, Q)
-    prob = torch.softmax(torch.bmm(key_mat, model.attention_net.linear(query_mat).transpose(2, 1)), dim=1)  # (B, k, q)
+    scores = torch.bmm(key_mat, model.attention_net.linear(query_mat).transpose(2, 1))                      # (B, k, q)
+    prob = sparsemax(scores, 1) if getattr(model, "sparse", False) else torch.softmax(scores, dim=1)
     if training or inference == "softmax":
         coef = prob
     elif inference == "activated":
@@ -336,9 +352,18 @@ def train_forward(model, bevs, trans_matrices=None, num_agent_tensor=None, batch
     if hasattr(model, "outc"):                      # segmentation variants: det backbone + 1x1 head, NHWC fp32 logits
         if hasattr(model, "stpn"):
             y = decoder(model.stpn.decoder, *encoder(model.stpn.encoder, x))
-        else:
+        else:                                       # the fusion stage by family, as the detection branches below (plain logits: no prob / coef)
             feats = encoder(model.u_encoder, x)
-            feats[model.layer] = v2v_fuse(model, feats[model.layer], trans_matrices.to(x.device), num_agent_tensor, batch_size)
+            T = trans_matrices.to(x.device)
+            if hasattr(model, "convgru"):
+                feats[model.layer] = v2v_fuse(model, feats[model.layer], T, num_agent_tensor, batch_size)
+            elif hasattr(model, "query_key_net"):
+                feats[model.layer] = when2com_fuse(model, x, feats[model.layer], T, num_agent_tensor, batch_size, model.training, inference)[0]
+            elif hasattr(model, "FUSE_MODE"):
+                fuse = disco_fuse if hasattr(model, "pixel_weighted_fusion") else simple_fuse
+                feats[model.layer] = fuse(model, feats[model.layer], T, num_agent_tensor, batch_size)
+            else:
+                raise NotImplementedError("training graph: a segmentation model of an unknown family")
             y = decoder(model.decoder, *feats)
         return model.outc.conv(y).permute(0, 2, 3, 1).contiguous()
     if hasattr(model, "stpn"):                      # FaFNet: lowerbound / upperbound

@@ -688,12 +688,34 @@ def _fused_on_fp32_graph(fuse, model, feat, *args):
     return (out.permute(0, 2, 3, 1).to(dtype=BF16, memory_format=torch.contiguous_format),) + tuple(extra)
 
 
-def _seg_decoder_output(model, x, T, num_agent_tensor, batch_size):
-    """The segmentation variants up to the decoder output (N, H, W, 32) bf16: the map the 1x1 class head reads."""
+def _fusion_stage(model, bevs, feats, T, num_agent_tensor, batch_size, inference):
+    """The cross-agent fusion of an intermediate model, detection or segmentation, chosen by family: feats[model.layer] is replaced by the
+    fused map.  -> the extra outputs of the family ({} but for when2com's prob_action / coef)."""
+    from . import graph
+    if hasattr(model, "convgru"):                   # V2VNet: the message-passing rounds on the kernels (v2v_fuse_nhwc); a ragged batch on the fp32 graph
+        feats[model.layer] = _v2v_stage(model, feats[model.layer], T, num_agent_tensor, batch_size)
+        return {}
+    if hasattr(model, "query_key_net"):             # when2com / who2com: its key / query tower reads the input on the fp32 graph
+        x32 = bevs[:, 0].permute(0, 3, 1, 2).to(torch.float32)
+        fused, prob, coef = _fused_on_fp32_graph(lambda m, f: graph.when2com_fuse(m, x32, f, T, num_agent_tensor, batch_size, model.training, inference),
+                                                 model, feats[model.layer])
+        feats[model.layer] = fused
+        return {"prob_action": prob, "coef": coef}
+    if hasattr(model, "FUSE_MODE"):                 # Sum / Mean / Max / Cat fusion, DiscoNet (no teacher)
+        fuse = graph.disco_fuse if hasattr(model, "pixel_weighted_fusion") else graph.simple_fuse
+        feats[model.layer], = _fused_on_fp32_graph(fuse, model, feats[model.layer], T, num_agent_tensor, batch_size)
+        return {}
+    raise NotImplementedError("hip_graph: unknown model family")
+
+
+def _seg_decoder_output(model, bevs, T, num_agent_tensor, batch_size, inference="softmax"):
+    """The segmentation variants up to the decoder output (N, H, W, 32) bf16: the map the 1x1 class head reads.  The fusion stage by family, as
+    in detection (_fusion_stage); when2com's prob_action / coef are not returned -- SegModule.step has no use for them."""
+    x = nhwc_input(bevs)
     if hasattr(model, "stpn"):
         return decoder(model.stpn.decoder, *encoder(model.stpn.encoder, x))
     feats = encoder(model.u_encoder, x)
-    feats[model.layer] = _v2v_stage(model, feats[model.layer], T, num_agent_tensor, batch_size)
+    _fusion_stage(model, bevs, feats, T, num_agent_tensor, batch_size, inference)
     return decoder(model.decoder, *feats)
 
 
@@ -754,7 +776,7 @@ def seg_train_loss(model, bevs, labels, trans_matrices=None, num_agent_tensor=No
     _rezero_arena()
     try:
         T = None if trans_matrices is None else trans_matrices.to(bevs.device)
-        y = _seg_decoder_output(model, nhwc_input(bevs), T, num_agent_tensor, batch_size)
+        y = _seg_decoder_output(model, bevs, T, num_agent_tensor, batch_size)
         return seg_head_loss(y, model.outc.conv.weight, model.outc.conv.bias, labels, weight, ignore_index)
     finally:
         _DEFER_COUNTERS[0] = prev
@@ -780,31 +802,17 @@ def _train_forward(model, bevs, trans_matrices=None, num_agent_tensor=None, batc
     train/graph.py::train_forward.  Every detection / segmentation baseline: encoder, decoder and heads on the kernels; the cross-agent
     fusion (V2VNet's warp + ConvGRU, when2com's handshake, sum / mean / max / cat / DiscoNet) on the fp32 graph at the fusion layer.
     model.training must be on."""
-    from . import graph
     if not bevs.is_cuda:
         raise RuntimeError("train/hip_graph.py runs on the MI355X (no CPU path)")
-    x = nhwc_input(bevs)
-    T = None if trans_matrices is None else trans_matrices.to(x.device)
+    T = None if trans_matrices is None else trans_matrices.to(bevs.device)
     if hasattr(model, "outc"):                      # segmentation variants: det backbone + 1x1 head, NHWC fp32 logits
-        y = _seg_decoder_output(model, x, T, num_agent_tensor, batch_size)
+        y = _seg_decoder_output(model, bevs, T, num_agent_tensor, batch_size, inference)
         return conv1x1(y, model.outc.conv.weight, model.outc.conv.bias, f32_out=True)
+    x = nhwc_input(bevs)
     if hasattr(model, "stpn"):                      # FaFNet: lowerbound / upperbound
         return heads(model, decoder(model.stpn.decoder, *encoder(model.stpn.encoder, x)))
     feats = encoder(model.u_encoder, x)
-    res_extra = {}
-    if hasattr(model, "convgru"):                   # V2VNet: the message-passing rounds on the kernels (v2v_fuse_nhwc); a ragged batch on the fp32 graph
-        feats[model.layer] = _v2v_stage(model, feats[model.layer], T, num_agent_tensor, batch_size)
-    elif hasattr(model, "query_key_net"):           # when2com / who2com: its key / query tower reads the input on the fp32 graph
-        x32 = bevs[:, 0].permute(0, 3, 1, 2).to(torch.float32)
-        fused, prob, coef = _fused_on_fp32_graph(lambda m, f: graph.when2com_fuse(m, x32, f, T, num_agent_tensor, batch_size, model.training, inference),
-                                                 model, feats[model.layer])
-        feats[model.layer] = fused
-        res_extra = {"prob_action": prob, "coef": coef}
-    elif hasattr(model, "FUSE_MODE"):               # Sum / Mean / Max / Cat fusion, DiscoNet (no teacher)
-        fuse = graph.disco_fuse if hasattr(model, "pixel_weighted_fusion") else graph.simple_fuse
-        feats[model.layer], = _fused_on_fp32_graph(fuse, model, feats[model.layer], T, num_agent_tensor, batch_size)
-    else:
-        raise NotImplementedError("hip_graph: unknown model family")
+    res_extra = _fusion_stage(model, bevs, feats, T, num_agent_tensor, batch_size, inference)
     res = heads(model, decoder(model.decoder, *feats))
     res.update(res_extra)
     return res

@@ -13,7 +13,8 @@ class SegModule(object):
             raise NotImplementedError("knowledge distillation is out of scope (DESIGN.md section 8)")
         self.model, self.config, self.optimizer = model, config, optimizer
         self.class_weight, self.ignore_index = class_weight, ignore_index     # train/loss.py::segmentation_loss (the switched-on paths of step)
-        self._graphed = None              # (batch-shape key, GraphedSegTrainStep) when TRAIN_SEG_GRAPH = 1
+        self.last_num_connect = None      # when2com variants: the communication rate of the last predict()
+        self._graphed = None            # (batch-shape key, GraphedSegTrainStep) when TRAIN_SEG_GRAPH = 1
         from .. import packing
         packing.watch_optimizer(optimizer)   # fused optimizers update the parameters without bumping their version counters
 
@@ -63,20 +64,28 @@ class SegModule(object):
             g = self.optimizer.__dict__.get("_v2x_graphed_steps", {}).get(self._graph_key(data, batch_size))
             if g is not None and not torch.equal(data["num_agent"].cpu(), g.num_agent):
                 return False
-        elif not hasattr(self.model, "stpn"):
-            return False
+        elif not hasattr(self.model, "stpn"):       # When2comSeg and the fusion family: no captured step exists for them -- their steps run eager
+            return False                            # (the kernel loss paths of step() still apply)
         return all(g.get("capturable", True) for g in self.optimizer.param_groups)
 
-    def predict(self, data, batch_size=1, label=None):
-        """-> (pred (A*B, X, Y) uint8, confusion matrix int64 [n_cls, n_cls] or None) on the HIP path."""
+    def predict(self, data, batch_size=1, label=None, inference=None):
+        """-> (pred (A*B, X, Y) uint8, confusion matrix int64 [n_cls, n_cls] or None) on the HIP path.  when2com variants: `inference`
+        ('softmax' | 'activated' | 'argmax_test', default 'activated') selects the links, and self.last_num_connect keeps the communication
+        rate of this batch (When2com.num_connect)."""
         from .. import ops
+        from ..models.det.FaFNet import FaFNet
+        from ..models.det.When2com import When2com
         self.model.eval()
         with torch.no_grad():
             x0 = self.model._input_nhwc(data["bev_seq"])
-            if hasattr(self.model, "fuse"):
-                logits = self.model.forward_nhwc(x0, data["trans_matrices"], data["num_agent"], batch_size=batch_size)
-            else:
+            if isinstance(self.model, FaFNet):          # lowerbound / upperbound: no exchange
                 logits = self.model.forward_nhwc(x0)
+            elif isinstance(self.model, When2com):
+                logits, _, coef = self.model.forward_nhwc(x0, data["trans_matrices"], data["num_agent"], training=False,
+                                                          inference=inference or "activated", batch_size=batch_size, return_handshake=True)
+                self.last_num_connect = When2com.num_connect(coef, self.model.agent_num)
+            else:                                       # V2VNetSeg and the fusion family
+                logits = self.model.forward_nhwc(x0, data["trans_matrices"], data["num_agent"], batch_size=batch_size)
         return ops.seg_argmax_confusion(logits, label)
 
 
