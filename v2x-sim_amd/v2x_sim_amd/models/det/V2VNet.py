@@ -36,6 +36,8 @@ class Conv2dGRU(torch.nn.Module):
 
 
 class V2VNet(IntermediateModelBase):
+    FAMILY = "v2v"
+
     def __init__(self, config, gnn_iter_times=1, layer=3, layer_channel=256, in_channels=13, num_agent=5,
                  compress_level=0, only_v2i=False, neighbor_source="initial"):
         super().__init__(config, layer, in_channels, kd_flag=0, num_agent=num_agent,
@@ -116,7 +118,7 @@ class V2VNet(IntermediateModelBase):
         if plan is None:
             plan = self.make_plan(num_agent_tensor, batch_size, x0.device)
         feats[self.layer] = self.fuse(feats[self.layer], trans_matrices, plan, batch_size, pk)
-        return self.decode_heads(pk, feats)
+        return self.head(pk, feats)
 
     def forward_points(self, points, n_pts, trans_matrices, num_agent_tensor, batch_size=1, grid=None, plan=None):
         """points -> logits on ONE GPU, the plain entry for raw sweeps: points (A*B, max_pts, stride >= 3) fp32 agent-major, n_pts (A*B,) int32.

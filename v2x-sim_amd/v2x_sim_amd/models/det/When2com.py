@@ -106,6 +106,8 @@ class MIMOGeneralDotProductAttention(_ParamsOnly):
 
 
 class When2com(IntermediateModelBase):
+    FAMILY = "when2com"
+
     def __init__(self, config, n_classes=21, in_channels=13, feat_channel=512, feat_squeezer=-1,
                  attention="additive", has_query=True, sparse=False, layer=3, warp_flag=1, image_size=512,
                  shared_img_encoder="unified", key_size=1024, query_size=32, num_agent=5, compress_level=0,
@@ -218,7 +220,7 @@ class When2com(IntermediateModelBase):
                      batch_size=1, plan=None):
         pk = self.packed(x0.device)
         feats, prob, coef = self.fused_feats(pk, x0, trans_matrices, num_agent_tensor, training, inference, batch_size, plan)
-        res = self.decode_heads(pk, feats)
+        res = self.head(pk, feats)
         res["prob_action"] = prob
         res["coef"] = coef
         return res
@@ -243,3 +245,6 @@ class When2com(IntermediateModelBase):
                                 batch_size)
         res["num_connect"] = self.num_connect(res["coef"], self.agent_num)
         return res
+
+    def run_batch(self, data, batch_size=1, inference=None):
+        return self(data["bev_seq"], data["trans_matrices"], data["num_agent"], training=False, inference=inference or "activated", batch_size=batch_size)

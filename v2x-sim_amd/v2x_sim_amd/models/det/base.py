@@ -204,6 +204,10 @@ class SingleRegressionHead(_ParamsOnly):
 class DetModelBase(nn.Module):
     """Abstract detection model (upstream DetModelBase): heads + agent<->batch helpers + the
     packed-parameter cache shared by every concrete model."""
+    # what a model says about itself ONCE; the training engines (train/graph.py, train/hip_graph.py) and the step modules (utils/) ask it instead
+    # of probing attributes.  "faf" | "v2v" | "when2com" | "fusion" | "disco" on the concrete classes, None on the abstract bases
+    FAMILY = None
+    last_num_connect = None        # when2com segmentation variants: the communication rate of the last run_batch()
 
     def __init__(self, config, layer=3, in_channels=13, kd_flag=True, p_com_outage=0.0, num_agent=5,
                  only_v2i=False):
@@ -245,6 +249,20 @@ class DetModelBase(nn.Module):
 
     def repack(self):
         self._packed = None
+
+    # ---- what every family answers ---------------------------------------------------------
+    def backbone(self):  # pragma: no cover - overridden
+        """-> (encoder, decoder): the two parameter containers, wherever the family keeps them."""
+        raise NotImplementedError
+
+    def head(self, pk, feats):
+        """What every forward_nhwc ends in: the detection heads here, the class head in models/seg."""
+        return self.decode_heads(pk, feats)
+
+    def run_batch(self, data, batch_size=1, inference=None):
+        """forward() on a batch dict ('bev_seq', 'trans_matrices', 'num_agent'): the one call of the step modules' inference paths.
+        `inference` is when2com's; the other families take no such argument."""
+        return self(data["bev_seq"], data["trans_matrices"], data["num_agent"], batch_size=batch_size)
 
     # ---- shared pieces --------------------------------------------------------------------
     def _pack_heads(self, device):
@@ -354,6 +372,9 @@ class IntermediateModelBase(DetModelBase):
         self._link_mask = None
         self.u_encoder = LidarEncoder(in_channels, compress_level=compress_level)
         self.decoder = LidarDecoder(in_channels)
+
+    def backbone(self):
+        return self.u_encoder, self.decoder
 
     # ---- who may talk to whom -------------------------------------------------------------
     def set_link_mask(self, mask):

@@ -63,22 +63,22 @@ class FusionBase(IntermediateModelBase):
         if plan is None:
             plan = self.make_plan(num_agent_tensor, batch_size, x0.device)
         feats[self.layer] = self.fuse(feats[self.layer], trans_matrices, plan, batch_size, pk)
-        return self.decode_heads(pk, feats)
+        return self.head(pk, feats)
 
     def forward(self, bevs, trans_matrices, num_agent_tensor, batch_size=1):
         return self.forward_nhwc(self._input_nhwc(bevs), trans_matrices, num_agent_tensor, batch_size)
 
 
 class SumFusion(FusionBase):
-    FUSE_MODE = V2X_FUSE_WSUM
+    FAMILY, FUSE_MODE = "fusion", V2X_FUSE_WSUM
 
 
 class MeanFusion(FusionBase):
-    FUSE_MODE = V2X_FUSE_MEAN
+    FAMILY, FUSE_MODE = "fusion", V2X_FUSE_MEAN
 
 
 class MaxFusion(FusionBase):
-    FUSE_MODE = V2X_FUSE_MAX
+    FAMILY, FUSE_MODE = "fusion", V2X_FUSE_MAX
 
 
 class ModulationLayer3(_ParamsOnly):
@@ -89,7 +89,7 @@ class ModulationLayer3(_ParamsOnly):
 
 
 class CatFusion(FusionBase):
-    FUSE_MODE = V2X_FUSE_MEAN
+    FAMILY, FUSE_MODE = "fusion", V2X_FUSE_MEAN
 
     def __init__(self, config, layer=3, in_channels=13, kd_flag=0, num_agent=5, compress_level=0, only_v2i=False):
         super().__init__(config, layer, in_channels, kd_flag, num_agent, compress_level, only_v2i)
@@ -125,7 +125,7 @@ class DiscoNet(FusionBase):
     MI355X mapping: one warp_fuse launch materialises every (ego, source) map (one-hot coefficients; the ego's own map is
     copied unwarped), the four 1x1 convs run as implicit-GEMM layers over the (item x source) batch with the concat as the
     two-source loader, and v2x_pixel_weighted_fuse does exp / normalise / weighted sum per pixel."""
-    FUSE_MODE = V2X_FUSE_WSUM
+    FAMILY, FUSE_MODE = "disco", V2X_FUSE_WSUM
 
     def __init__(self, config, layer=3, in_channels=13, kd_flag=0, num_agent=5, compress_level=0, only_v2i=False):
         super().__init__(config, layer, in_channels, kd_flag, num_agent, compress_level, only_v2i)

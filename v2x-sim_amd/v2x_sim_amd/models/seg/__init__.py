@@ -5,14 +5,15 @@ unverified, so the build-owned spec reuses the detection backbone
 and replaces the det heads by a 1x1 conv 32 -> n_classes producing NHWC fp32 logits
 (DESIGN.md section 3.6).  n_classes = 8 as recollected for V2X-Sim.
 
-Every --com of detection except `late` has its class here: the detection twin plus `outc`, the twin's forward up to the fused pyramid, then
-_seg_tail (decoder + class head) in place of the detection heads.
+Every --com of detection except `late` has its class here, and every one is `class XSeg(SegHeadMixin, X)`: the detection twin (its FAMILY, its
+backbone(), its forward_nhwc) with `outc` added and head() -- what forward_nhwc ends in -- answering decoder + class head instead of the detection heads.
 """
+import torch
 import torch.nn as nn
 
 from ... import ops, packing, tuning
 from ..._lib import V2X_EPI_F32
-from ..det.base import LidarDecoder, LidarEncoder, _ParamsOnly
+from ..det.base import LidarDecoder, _ParamsOnly
 from ..det.FaFNet import FaFNet
 from ..det.fusion import CatFusion, DiscoNet, MaxFusion, MeanFusion, SumFusion
 from ..det.V2VNet import V2VNet
@@ -25,41 +26,11 @@ class OutConv(_ParamsOnly):
         self.conv = nn.Conv2d(cin, n_classes, kernel_size=1)
 
 
-def _pack_seg_head(outc, device):
-    scale, shift = packing.fold_bn(outc.conv.bias, None, outc.conv.out_channels)
-    return packing.pack_conv("outc", outc.conv.weight, scale, shift, stride=1, pad=0, relu=False,
-                             epilogue=V2X_EPI_F32, device=device)
-
-
-def _pack_seg_fused(decoder, outc, device):
-    """conv8_2 (3x3 32 -> 32, BN, ReLU) chained with the 1x1 class head in ONE halo launch (conv_halo.hip: <0, 32, 32, 16, 2>): the 32-channel
-    map is rounded to bf16 exactly as the stand-alone layer stores it but never reaches HBM (-1.3 GB written and read back per 320 maps, and the
-    gather kernel's two launches for the head).  None when the head has more than 16 classes (one padded channel tile) or a class count that
-    is not a multiple of 4 (the chained fp32 epilogue stores whole float4s per k-slot quarter; v2x_conv2d(halo) requires Cout2 % 4 == 0): such
-    heads keep the two-layer path."""
-    import torch
-    n_cls = outc.conv.out_channels
-    if n_cls > 16 or n_cls % 4 != 0 or decoder.conv8_2.out_channels != 32 or decoder.conv8_2.in_channels != 32:
-        return None
-    s1, t1 = packing.fold_bn(decoder.conv8_2.bias, decoder.bn8_2, 32)
-    w2 = outc.conv.weight.detach().float().cpu()
-    b2 = outc.conv.bias.detach().float().cpu() if outc.conv.bias is not None else torch.zeros(n_cls)
-    return packing.pack_conv_halo("decoder.conv8_2+outc", decoder.conv8_2.weight, s1, t1, relu=True, chain=(w2, torch.ones(n_cls), b2, False),
-                                  epilogue=V2X_EPI_F32, device=device)
-
-
-def _seg_tail(pk, feats):
-    """Decoder + class head -> fp32 NHWC logits; conv8_2 and the head as one launch where the map tiles (tuning switch SEG_FUSE)."""
-    fused = pk.get("seg_fused")
-    x0 = feats[0]
-    if fused is not None and tuning.get("SEG_FUSE") != 0 and ops.halo_eligible(x0.shape[1], x0.shape[2], 1, 32):
-        return ops.conv2d(fused, LidarDecoder.run(pk["dec"], *feats, last=False))
-    return ops.conv2d(pk["seg"], LidarDecoder.run(pk["dec"], *feats))
-
-
-class V2VNetSeg(V2VNet):
-    """forward -> logits (A*B, 256, 256, n_classes) fp32 NHWC (upstream returns NCHW; argmax / CE are
-    layout-agnostic, and ops.seg_argmax_confusion consumes NHWC directly)."""
+class SegHeadMixin(object):
+    """The class head on a detection twin: `class XSeg(SegHeadMixin, X)`.  The twin's constructor, then `outc`; the twin's packing plus `seg` /
+    `seg_fused`; the twin's forward_nhwc itself, which ends in self.head -- here decoder + 1x1 class head -> logits (N, X, Y, n_classes) fp32 NHWC
+    (upstream returns NCHW; argmax / CE are layout-agnostic, and ops.seg_argmax_confusion consumes NHWC directly).  Link masks, compress_level
+    and the bit-grid input (zbits) are whatever the twin takes."""
 
     def __init__(self, config, n_classes=8, **kw):
         super().__init__(config, **kw)
@@ -68,54 +39,49 @@ class V2VNetSeg(V2VNet):
 
     def _pack(self, device):
         pk = super()._pack(device)
-        pk["seg"] = _pack_seg_head(self.outc, device)
-        pk["seg_fused"] = _pack_seg_fused(self.decoder, self.outc, device)
+        conv = self.outc.conv
+        scale, shift = packing.fold_bn(conv.bias, None, conv.out_channels)
+        pk["seg"] = packing.pack_conv("outc", conv.weight, scale, shift, stride=1, pad=0, relu=False, epilogue=V2X_EPI_F32, device=device)
+        pk["seg_fused"] = self._pack_fused(self.backbone()[1], device)
         return pk
 
-    @ops.latency_entry
-    def forward_nhwc(self, x0, trans_matrices, num_agent_tensor, batch_size=1, plan=None, zbits=0):
-        """x0: (A*B, X, Y, 32) bf16 NHWC, or -- zbits > 0 -- the voxeliser's int32 bit grid (A*B, X, Y) with zbits height bins."""
-        pk = self.packed(x0.device)
-        feats = LidarEncoder.run(pk["enc"], x0, zbits=zbits)
-        if plan is None:
-            plan = self.make_plan(num_agent_tensor, batch_size, x0.device)
-        feats[self.layer] = self.fuse(feats[self.layer], trans_matrices, plan, batch_size, pk)
-        return _seg_tail(pk, feats)
+    def _pack_fused(self, decoder, device):
+        """conv8_2 (3x3 32 -> 32, BN, ReLU) chained with the 1x1 class head in ONE halo launch (conv_halo.hip: <0, 32, 32, 16, 2>): the 32-channel
+        map is rounded to bf16 exactly as the stand-alone layer stores it but never reaches HBM (-1.3 GB written and read back per 320 maps, and the
+        gather kernel's two launches for the head).  None when the head has more than 16 classes (one padded channel tile) or a class count that
+        is not a multiple of 4 (the chained fp32 epilogue stores whole float4s per k-slot quarter; v2x_conv2d(halo) requires Cout2 % 4 == 0): such
+        heads keep the two-layer path."""
+        conv = self.outc.conv
+        n_cls = conv.out_channels
+        if n_cls > 16 or n_cls % 4 != 0 or decoder.conv8_2.out_channels != 32 or decoder.conv8_2.in_channels != 32:
+            return None
+        s1, t1 = packing.fold_bn(decoder.conv8_2.bias, decoder.bn8_2, 32)
+        w2 = conv.weight.detach().float().cpu()
+        b2 = conv.bias.detach().float().cpu() if conv.bias is not None else torch.zeros(n_cls)
+        return packing.pack_conv_halo("decoder.conv8_2+outc", decoder.conv8_2.weight, s1, t1, relu=True, chain=(w2, torch.ones(n_cls), b2, False),
+                                      epilogue=V2X_EPI_F32, device=device)
+
+    def head(self, pk, feats):
+        """Decoder + class head -> fp32 NHWC logits; conv8_2 and the head as one launch where the map tiles (tuning switch SEG_FUSE)."""
+        fused = pk.get("seg_fused")
+        x0 = feats[0]
+        if fused is not None and tuning.get("SEG_FUSE") != 0 and ops.halo_eligible(x0.shape[1], x0.shape[2], 1, 32):
+            return ops.conv2d(fused, LidarDecoder.run(pk["dec"], *feats, last=False))
+        return ops.conv2d(pk["seg"], LidarDecoder.run(pk["dec"], *feats))
 
 
-class FaFNetSeg(FaFNet):
-    def __init__(self, config, n_classes=8, **kw):
-        super().__init__(config, **kw)
-        self.n_classes = n_classes
-        self.outc = OutConv(32, n_classes)
-
-    def _pack(self, device):
-        pk = super()._pack(device)
-        pk["seg"] = _pack_seg_head(self.outc, device)
-        pk["seg_fused"] = _pack_seg_fused(self.stpn.decoder, self.outc, device)
-        return pk
-
-    @ops.latency_entry
-    def forward_nhwc(self, x0, zbits=0):
-        pk = self.packed(x0.device)
-        feats = LidarEncoder.run(pk["enc"], x0, zbits=zbits)
-        return _seg_tail(pk, feats)
+class FaFNetSeg(SegHeadMixin, FaFNet):
+    pass
 
 
-class When2comSeg(When2com):
+class V2VNetSeg(SegHeadMixin, V2VNet):
+    pass
+
+
+class When2comSeg(SegHeadMixin, When2com):
     """when2com / who2com with the class head: the handshake and the weighted warp-sum of the detection model (When2com.fused_feats), then
-    decoder + 1x1 head.  Every constructor switch of When2com, `sparse` (sparsemax) included; a link mask raises as there."""
-
-    def __init__(self, config, n_classes=8, **kw):
-        super().__init__(config, **kw)
-        self.n_classes = n_classes
-        self.outc = OutConv(32, n_classes)
-
-    def _pack(self, device):
-        pk = super()._pack(device)
-        pk["seg"] = _pack_seg_head(self.outc, device)
-        pk["seg_fused"] = _pack_seg_fused(self.decoder, self.outc, device)
-        return pk
+    decoder + 1x1 head.  Every constructor switch of When2com, `sparse` (sparsemax) included; a link mask raises as there.  What differs from the
+    twin: forward_nhwc returns the logits (not a dict), the handshake on request, and forward has no maps / vis / MO_flag."""
 
     @ops.latency_entry
     def forward_nhwc(self, x0, trans_matrices, num_agent_tensor, training=True, inference="activated", batch_size=1, plan=None,
@@ -123,55 +89,36 @@ class When2comSeg(When2com):
         """-> logits (A*B, X, Y, n_classes) fp32 NHWC; return_handshake=True: (logits, prob, coef), the two (B, A_key, A_query)."""
         pk = self.packed(x0.device)
         feats, prob, coef = self.fused_feats(pk, x0, trans_matrices, num_agent_tensor, training, inference, batch_size, plan)
-        logits = _seg_tail(pk, feats)
+        logits = self.head(pk, feats)
         return (logits, prob, coef) if return_handshake else logits
 
     def forward(self, bevs, trans_matrices, num_agent_tensor, training=True, inference="activated", batch_size=1):
         return self.forward_nhwc(self._input_nhwc(bevs), trans_matrices, num_agent_tensor, training, inference, batch_size)
 
-
-class _FusionSegMixin(object):
-    """The class head on a FusionBase model: FusionBase.forward_nhwc with _seg_tail in place of decode_heads.  Link masks and compress_level are
-    the twin's (make_plan / the encoder's codec); the bit-grid input (zbits) is not taken, as in the twins."""
-
-    def __init__(self, config, n_classes=8, **kw):
-        super().__init__(config, **kw)
-        self.n_classes = n_classes
-        self.outc = OutConv(32, n_classes)
-
-    def _pack(self, device):
-        pk = super()._pack(device)
-        pk["seg"] = _pack_seg_head(self.outc, device)
-        pk["seg_fused"] = _pack_seg_fused(self.decoder, self.outc, device)
-        return pk
-
-    @ops.latency_entry
-    def forward_nhwc(self, x0, trans_matrices, num_agent_tensor, batch_size=1, plan=None):
-        pk = self.packed(x0.device)
-        feats = LidarEncoder.run(pk["enc"], x0)
-        if plan is None:
-            plan = self.make_plan(num_agent_tensor, batch_size, x0.device)
-        feats[self.layer] = self.fuse(feats[self.layer], trans_matrices, plan, batch_size, pk)
-        return _seg_tail(pk, feats)
+    def run_batch(self, data, batch_size=1, inference=None):
+        logits, _, coef = self.forward_nhwc(self._input_nhwc(data["bev_seq"]), data["trans_matrices"], data["num_agent"], False,
+                                            inference or "activated", batch_size, return_handshake=True)
+        self.last_num_connect = self.num_connect(coef, self.agent_num)
+        return logits
 
 
-class SumFusionSeg(_FusionSegMixin, SumFusion):
+class SumFusionSeg(SegHeadMixin, SumFusion):
     pass
 
 
-class MeanFusionSeg(_FusionSegMixin, MeanFusion):
+class MeanFusionSeg(SegHeadMixin, MeanFusion):
     pass
 
 
-class MaxFusionSeg(_FusionSegMixin, MaxFusion):
+class MaxFusionSeg(SegHeadMixin, MaxFusion):
     pass
 
 
-class CatFusionSeg(_FusionSegMixin, CatFusion):
+class CatFusionSeg(SegHeadMixin, CatFusion):
     pass
 
 
-class DiscoNetSeg(_FusionSegMixin, DiscoNet):
+class DiscoNetSeg(SegHeadMixin, DiscoNet):
     pass
 
 

@@ -341,48 +341,50 @@ def disco_fuse(model, feat, trans, num_agent_tensor, B):
     return feat.index_copy(0, rows_t, fused)
 
 
+def _when2com_stage(model, x, feat, T, num_agent_tensor, B, inference):
+    fused, prob, coef = when2com_fuse(model, x, feat, T, num_agent_tensor, B, model.training, inference)
+    return fused, {"prob_action": prob, "coef": coef}
+
+
+# model.FAMILY -> (model, x, feat, T, num_agent_tensor, B, inference) -> (the fused fusion-layer map, the family's extra outputs); None: no exchange
+FUSION_STAGES = {"faf": None,
+                 "v2v": lambda model, x, feat, T, nat, B, inference: (v2v_fuse(model, feat, T, nat, B), {}),
+                 "when2com": _when2com_stage,
+                 "fusion": lambda model, x, feat, T, nat, B, inference: (simple_fuse(model, feat, T, nat, B), {}),
+                 "disco": lambda model, x, feat, T, nat, B, inference: (disco_fuse(model, feat, T, nat, B), {})}
+
+
+def fusion_stage_of(stages, model):
+    """The fusion stage of the model's family in an engine's table; a family the table does not know has no training graph."""
+    if model.FAMILY not in stages:
+        raise NotImplementedError("training graph: no fusion stage for the family %r of %s" % (model.FAMILY, type(model).__name__))
+    return stages[model.FAMILY]
+
+
+def _fusion_stage(model, x, feats, trans_matrices, num_agent_tensor, batch_size, inference):
+    """The cross-agent fusion, detection or segmentation: feats[model.layer] is replaced by the fused map.  -> the family's extra outputs."""
+    stage = fusion_stage_of(FUSION_STAGES, model)
+    if stage is None:
+        return {}
+    feats[model.layer], extras = stage(model, x, feats[model.layer], trans_matrices.to(x.device), num_agent_tensor, batch_size, inference)
+    return extras
+
+
 def train_forward(model, bevs, trans_matrices=None, num_agent_tensor=None, batch_size=1, inference="softmax"):
-    """bevs (A*B, 1, X, Y, Z) dense occupancy (the Dataset format) -> {'loc', 'cls'} with the shapes of the HIP path.
+    """bevs (A*B, 1, X, Y, Z) dense occupancy (the Dataset format) -> {'loc', 'cls'} with the shapes of the HIP path (+ when2com's
+    'prob_action' / 'coef'); a segmentation variant (a model with the `outc` class head): NHWC fp32 logits.
     Uses batch-statistics BN when model.training, running statistics otherwise.
     V2X_TRAIN_HIP=1: in train mode encoder, decoder and heads run as the bf16 NHWC graph on the hand-written kernels (train/hip_graph.py)."""
     if tuning.get("TRAIN_HIP") == 1 and model.training and bevs.is_cuda:
         from . import hip_graph
         return hip_graph.train_forward(model, bevs, trans_matrices, num_agent_tensor, batch_size, inference)
     x = bevs[:, 0].permute(0, 3, 1, 2).to(torch.float32)
-    if hasattr(model, "outc"):                      # segmentation variants: det backbone + 1x1 head, NHWC fp32 logits
-        if hasattr(model, "stpn"):
-            y = decoder(model.stpn.decoder, *encoder(model.stpn.encoder, x))
-        else:                                       # the fusion stage by family, as the detection branches below (plain logits: no prob / coef)
-            feats = encoder(model.u_encoder, x)
-            T = trans_matrices.to(x.device)
-            if hasattr(model, "convgru"):
-                feats[model.layer] = v2v_fuse(model, feats[model.layer], T, num_agent_tensor, batch_size)
-            elif hasattr(model, "query_key_net"):
-                feats[model.layer] = when2com_fuse(model, x, feats[model.layer], T, num_agent_tensor, batch_size, model.training, inference)[0]
-            elif hasattr(model, "FUSE_MODE"):
-                fuse = disco_fuse if hasattr(model, "pixel_weighted_fusion") else simple_fuse
-                feats[model.layer] = fuse(model, feats[model.layer], T, num_agent_tensor, batch_size)
-            else:
-                raise NotImplementedError("training graph: a segmentation model of an unknown family")
-            y = decoder(model.decoder, *feats)
+    enc, dec = model.backbone()
+    feats = encoder(enc, x)
+    extras = _fusion_stage(model, x, feats, trans_matrices, num_agent_tensor, batch_size, inference)
+    y = decoder(dec, *feats)
+    if hasattr(model, "outc"):
         return model.outc.conv(y).permute(0, 2, 3, 1).contiguous()
-    if hasattr(model, "stpn"):                      # FaFNet: lowerbound / upperbound
-        feats = encoder(model.stpn.encoder, x)
-        return heads(model, decoder(model.stpn.decoder, *feats))
-    if hasattr(model, "convgru"):                   # V2VNet
-        feats = encoder(model.u_encoder, x)
-        feats[model.layer] = v2v_fuse(model, feats[model.layer], trans_matrices.to(x.device), num_agent_tensor, batch_size)
-        return heads(model, decoder(model.decoder, *feats))
-    if hasattr(model, "query_key_net"):             # when2com / who2com
-        feats = encoder(model.u_encoder, x)
-        feats[model.layer], prob, coef = when2com_fuse(model, x, feats[model.layer], trans_matrices.to(x.device),
-                                                       num_agent_tensor, batch_size, model.training, inference)
-        res = heads(model, decoder(model.decoder, *feats))
-        res["prob_action"], res["coef"] = prob, coef
-        return res
-    if hasattr(model, "FUSE_MODE"):                 # Sum / Mean / Max / Cat fusion, DiscoNet (no teacher)
-        feats = encoder(model.u_encoder, x)
-        fuse = disco_fuse if hasattr(model, "pixel_weighted_fusion") else simple_fuse
-        feats[model.layer] = fuse(model, feats[model.layer], trans_matrices.to(x.device), num_agent_tensor, batch_size)
-        return heads(model, decoder(model.decoder, *feats))
-    raise NotImplementedError("training graph exists for FaFNet, V2VNet, When2com and the FusionBase family")
+    res = heads(model, y)
+    res.update(extras)
+    return res

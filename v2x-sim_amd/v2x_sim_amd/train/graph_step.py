@@ -15,6 +15,30 @@ from .loss import detection_loss
 _KEYS = ("bev_seq", "labels", "reg_targets", "reg_loss_mask", "trans_matrices")
 
 
+def capture_ok(model, optimizer, data, cached):
+    """The scope above as one rule, by model.FAMILY: "faf" always; "v2v" unless `cached` -- the step already captured for this batch shape, or
+    None -- was captured with another agent table; every other family runs eager.  And every param group must be capturable."""
+    if model.FAMILY == "v2v":
+        if cached is not None and not torch.equal(data["num_agent"].cpu(), cached.num_agent):
+            return False
+    elif model.FAMILY != "faf":
+        return False
+    return all(g.get("capturable", True) for g in optimizer.param_groups)
+
+
+def cached_step(optimizer, key, build=None):
+    """The captured step of one batch shape.  The steps live ON THE OPTIMIZER (one per batch shape), not on the step module: the training loops
+    build a new module per epoch around the run's one optimizer, and a step re-captured every epoch (or for the partial last batch and back)
+    would pay its warm-up each time.  (The warm-up itself restores whatever optimizer state it finds.)  build: called when the key is new;
+    without it -> the step or None, and the optimizer is left as it is."""
+    if build is None:
+        return optimizer.__dict__.get("_v2x_graphed_steps", {}).get(key)
+    cache = optimizer.__dict__.setdefault("_v2x_graphed_steps", {})
+    if key not in cache:
+        cache[key] = build()
+    return cache[key]
+
+
 class GraphedTrainStep:
     _keys = _KEYS          # the batch entries copied into static tensors (GraphedSegTrainStep: its own)
 

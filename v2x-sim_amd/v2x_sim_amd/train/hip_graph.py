@@ -22,6 +22,7 @@ Packed weights are rebuilt on the GPU after every optimizer step (packing.on_dev
 Mixed precision: activations, activation gradients and the MFMA operands are bf16; every sum, the BN statistics, the weight
 gradients and the master weights are fp32.  Enabled with V2X_TRAIN_HIP=1 (FaFModule.step / train_forward); there is no CPU path.
 """
+import contextlib
 import types
 import weakref
 
@@ -29,6 +30,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops, packing, tuning
+from . import graph
 
 BF16 = torch.bfloat16
 
@@ -664,18 +666,9 @@ def v2v_fuse_nhwc(model, feat, trans, num_agent_tensor, B):
     return cur
 
 
-def _v2v_stage(model, feat, T, num_agent_tensor, batch_size):
-    from . import graph
-    out = v2v_fuse_nhwc(model, feat, T, num_agent_tensor, batch_size)
-    if out is None:      # warp + gate arithmetic on the fp32 graph, the GRU's convolution on the kernels (rounds 3-5's form)
-        out, = _fused_on_fp32_graph(graph.v2v_fuse, model, feat, T, num_agent_tensor, batch_size, _gru_conv_hip)
-    return out
-
-
 def _fused_on_fp32_graph(fuse, model, feat, *args):
     """The cross-agent fusion runs on the fp32 NCHW graph (train/graph.py): convert the fusion-layer maps, fuse, convert back.  The warp
     inside it (graph.warp_batch) runs on the hand-written kernels, forward and backward (WARP_HIP=0: F.grid_sample and its atomic backward)."""
-    from . import graph
     prev = graph._affine_sample_override
     graph._affine_sample_override = _AffineSample.apply if tuning.get("WARP_HIP") != 0 else None
     try:
@@ -688,35 +681,32 @@ def _fused_on_fp32_graph(fuse, model, feat, *args):
     return (out.permute(0, 2, 3, 1).to(dtype=BF16, memory_format=torch.contiguous_format),) + tuple(extra)
 
 
-def _fusion_stage(model, bevs, feats, T, num_agent_tensor, batch_size, inference):
-    """The cross-agent fusion of an intermediate model, detection or segmentation, chosen by family: feats[model.layer] is replaced by the
-    fused map.  -> the extra outputs of the family ({} but for when2com's prob_action / coef)."""
-    from . import graph
-    if hasattr(model, "convgru"):                   # V2VNet: the message-passing rounds on the kernels (v2v_fuse_nhwc); a ragged batch on the fp32 graph
-        feats[model.layer] = _v2v_stage(model, feats[model.layer], T, num_agent_tensor, batch_size)
-        return {}
-    if hasattr(model, "query_key_net"):             # when2com / who2com: its key / query tower reads the input on the fp32 graph
-        x32 = bevs[:, 0].permute(0, 3, 1, 2).to(torch.float32)
-        fused, prob, coef = _fused_on_fp32_graph(lambda m, f: graph.when2com_fuse(m, x32, f, T, num_agent_tensor, batch_size, model.training, inference),
-                                                 model, feats[model.layer])
-        feats[model.layer] = fused
-        return {"prob_action": prob, "coef": coef}
-    if hasattr(model, "FUSE_MODE"):                 # Sum / Mean / Max / Cat fusion, DiscoNet (no teacher)
-        fuse = graph.disco_fuse if hasattr(model, "pixel_weighted_fusion") else graph.simple_fuse
-        feats[model.layer], = _fused_on_fp32_graph(fuse, model, feats[model.layer], T, num_agent_tensor, batch_size)
-        return {}
-    raise NotImplementedError("hip_graph: unknown model family")
+def _v2v_stage(model, bevs, feat, T, num_agent_tensor, batch_size, inference):
+    """V2VNet: the message-passing rounds on the kernels (v2v_fuse_nhwc); a batch that form does not cover: warp + gate arithmetic on the fp32
+    graph, the GRU's convolution on the kernels (rounds 3-5's form)."""
+    out = v2v_fuse_nhwc(model, feat, T, num_agent_tensor, batch_size)
+    if out is None:
+        out, = _fused_on_fp32_graph(graph.v2v_fuse, model, feat, T, num_agent_tensor, batch_size, _gru_conv_hip)
+    return out, {}
 
 
-def _seg_decoder_output(model, bevs, T, num_agent_tensor, batch_size, inference="softmax"):
-    """The segmentation variants up to the decoder output (N, H, W, 32) bf16: the map the 1x1 class head reads.  The fusion stage by family, as
-    in detection (_fusion_stage); when2com's prob_action / coef are not returned -- SegModule.step has no use for them."""
-    x = nhwc_input(bevs)
-    if hasattr(model, "stpn"):
-        return decoder(model.stpn.decoder, *encoder(model.stpn.encoder, x))
-    feats = encoder(model.u_encoder, x)
-    _fusion_stage(model, bevs, feats, T, num_agent_tensor, batch_size, inference)
-    return decoder(model.decoder, *feats)
+def _when2com_stage(model, bevs, feat, T, num_agent_tensor, batch_size, inference):
+    """when2com / who2com: its key / query tower reads the input on the fp32 graph."""
+    x32 = bevs[:, 0].permute(0, 3, 1, 2).to(torch.float32)
+    fused, prob, coef = _fused_on_fp32_graph(lambda m, f: graph.when2com_fuse(m, x32, f, T, num_agent_tensor, batch_size, model.training, inference),
+                                             model, feat)
+    return fused, {"prob_action": prob, "coef": coef}
+
+
+def _fp32_stage(fuse):
+    """Sum / Mean / Max / Cat fusion, DiscoNet (no teacher): the fp32 graph's stage as it is."""
+    return lambda model, bevs, feat, T, nat, B, inference: (_fused_on_fp32_graph(fuse, model, feat, T, nat, B)[0], {})
+
+
+# model.FAMILY -> (model, bevs, feat, T, num_agent_tensor, B, inference) -> (the fused fusion-layer map, the family's extra outputs); None: no
+# exchange.  graph.py's table on this engine: the same families, detection and segmentation alike
+FUSION_STAGES = {"faf": None, "v2v": _v2v_stage, "when2com": _when2com_stage, "fusion": _fp32_stage(graph.simple_fuse),
+                 "disco": _fp32_stage(graph.disco_fuse)}
 
 
 class _SegHeadLoss(torch.autograd.Function):
@@ -764,55 +754,56 @@ def seg_head_loss(y, weight, bias, labels, class_weight=None, ignore_index=255):
     return segmentation_loss(conv1x1(y, weight, bias, f32_out=True), labels, class_weight, ignore_index)
 
 
+@contextlib.contextmanager
+def _forward_scope():
+    """One forward pass: the stale packings rebuilt and the zero arena re-zeroed first; the BatchNorm layers' num_batches_tracked counters
+    bumped together, in one launch, when the pass is complete."""
+    prev, _DEFER_COUNTERS[0] = _DEFER_COUNTERS[0], True
+    _repack_stale()
+    _rezero_arena()
+    try:
+        yield
+    finally:
+        _DEFER_COUNTERS[0] = prev
+        if not prev:
+            _flush_counters()
+
+
+def _decoder_output(model, bevs, trans_matrices, num_agent_tensor, batch_size, inference):
+    """The one path of every baseline, detection or segmentation: input, encoder, the family's fusion stage, decoder.  -> (the decoder output
+    (N, H, W, 32) bf16 -- the map the heads read --, the family's extra outputs: {} but for when2com's prob_action / coef)."""
+    if not bevs.is_cuda:
+        raise RuntimeError("train/hip_graph.py runs on the MI355X (no CPU path)")
+    T = None if trans_matrices is None else trans_matrices.to(bevs.device)
+    enc, dec = model.backbone()
+    feats = encoder(enc, nhwc_input(bevs))
+    stage = graph.fusion_stage_of(FUSION_STAGES, model)
+    extras = {}
+    if stage is not None:
+        feats[model.layer], extras = stage(model, bevs, feats[model.layer], T, num_agent_tensor, batch_size, inference)
+    return decoder(dec, *feats), extras
+
+
 def seg_train_loss(model, bevs, labels, trans_matrices=None, num_agent_tensor=None, batch_size=1, weight=None, ignore_index=255):
-    """One forward pass of a segmentation variant to its LOSS: the seg branch of _train_forward up to the decoder output, then seg_head_loss.
+    """One forward pass of a segmentation variant to its LOSS: train_forward's path up to the decoder output, then seg_head_loss (when2com's
+    prob_action / coef are dropped -- SegModule.step has no use for them).
     bevs (A*B, 1, X, Y, Z) on the MI355X, labels (A*B, X, Y) -> the scalar loss (model.training must be on)."""
     if not hasattr(model, "outc"):
         raise ValueError("seg_train_loss: a segmentation variant (a model with an `outc` class head) is needed")
-    if not bevs.is_cuda:
-        raise RuntimeError("train/hip_graph.py runs on the MI355X (no CPU path)")
-    prev, _DEFER_COUNTERS[0] = _DEFER_COUNTERS[0], True
-    _repack_stale()
-    _rezero_arena()
-    try:
-        T = None if trans_matrices is None else trans_matrices.to(bevs.device)
-        y = _seg_decoder_output(model, bevs, T, num_agent_tensor, batch_size)
+    with _forward_scope():
+        y, _ = _decoder_output(model, bevs, trans_matrices, num_agent_tensor, batch_size, "softmax")
         return seg_head_loss(y, model.outc.conv.weight, model.outc.conv.bias, labels, weight, ignore_index)
-    finally:
-        _DEFER_COUNTERS[0] = prev
-        if not prev:
-            _flush_counters()
 
 
 def train_forward(model, bevs, trans_matrices=None, num_agent_tensor=None, batch_size=1, inference="softmax"):
-    """See _train_forward; the BatchNorm layers' num_batches_tracked counters are bumped together, in one launch, when the forward is complete."""
-    prev, _DEFER_COUNTERS[0] = _DEFER_COUNTERS[0], True
-    _repack_stale()
-    _rezero_arena()
-    try:
-        return _train_forward(model, bevs, trans_matrices, num_agent_tensor, batch_size, inference)
-    finally:
-        _DEFER_COUNTERS[0] = prev
-        if not prev:
-            _flush_counters()
-
-
-def _train_forward(model, bevs, trans_matrices=None, num_agent_tensor=None, batch_size=1, inference="softmax"):
     """bevs (A*B, 1, X, Y, Z) on the MI355X -> {'loc', 'cls'} fp32 (segmentation variants: NHWC fp32 logits), shapes as
     train/graph.py::train_forward.  Every detection / segmentation baseline: encoder, decoder and heads on the kernels; the cross-agent
     fusion (V2VNet's warp + ConvGRU, when2com's handshake, sum / mean / max / cat / DiscoNet) on the fp32 graph at the fusion layer.
     model.training must be on."""
-    if not bevs.is_cuda:
-        raise RuntimeError("train/hip_graph.py runs on the MI355X (no CPU path)")
-    T = None if trans_matrices is None else trans_matrices.to(bevs.device)
-    if hasattr(model, "outc"):                      # segmentation variants: det backbone + 1x1 head, NHWC fp32 logits
-        y = _seg_decoder_output(model, bevs, T, num_agent_tensor, batch_size, inference)
-        return conv1x1(y, model.outc.conv.weight, model.outc.conv.bias, f32_out=True)
-    x = nhwc_input(bevs)
-    if hasattr(model, "stpn"):                      # FaFNet: lowerbound / upperbound
-        return heads(model, decoder(model.stpn.decoder, *encoder(model.stpn.encoder, x)))
-    feats = encoder(model.u_encoder, x)
-    res_extra = _fusion_stage(model, bevs, feats, T, num_agent_tensor, batch_size, inference)
-    res = heads(model, decoder(model.decoder, *feats))
-    res.update(res_extra)
-    return res
+    with _forward_scope():
+        y, extras = _decoder_output(model, bevs, trans_matrices, num_agent_tensor, batch_size, inference)
+        if hasattr(model, "outc"):
+            return conv1x1(y, model.outc.conv.weight, model.outc.conv.bias, f32_out=True)
+        res = heads(model, y)
+        res.update(extras)
+        return res

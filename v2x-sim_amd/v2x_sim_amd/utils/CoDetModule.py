@@ -60,16 +60,11 @@ class FaFModule(object):
         self.model.train()
         if self._graph_ok(data, batch_size):
             # V2X_TRAIN_HIP=1 V2X_TRAIN_GRAPH=1: the whole step as one hipGraph (train/graph_step.py), rebuilt when the batch shape changes
-            from ..train.graph_step import GraphedTrainStep
-            # The captured steps live ON THE OPTIMIZER (one per batch shape), not on this module: the training loops build a new FaFModule
-            # per epoch around the run's one optimizer, and a step re-captured every epoch (or for the partial last batch and back) would
-            # pay its warm-up each time.  (The warm-up itself restores whatever optimizer state it finds: graph_step.py.)
+            from ..train.graph_step import GraphedTrainStep, cached_step
             key = self._graph_key(data, batch_size)
-            cache = self.optimizer.__dict__.setdefault("_v2x_graphed_steps", {})
-            if key not in cache:
-                cache[key] = GraphedTrainStep(self.model, self.optimizer, data, batch_size, normalizer=self.loss_normalizer)
-            self._graphed = (key, cache[key])
-            loss, cls_loss, loc_loss = cache[key](data)
+            step = cached_step(self.optimizer, key, lambda: GraphedTrainStep(self.model, self.optimizer, data, batch_size, normalizer=self.loss_normalizer))
+            self._graphed = (key, step)
+            loss, cls_loss, loc_loss = step(data)
             return loss.item(), cls_loss.item(), loc_loss.item()
         result = train_forward(self.model, bev, data.get("trans_matrices"), data.get("num_agent"), batch_size)
         loss, cls_loss, loc_loss = detection_loss(result, data["labels"], data["reg_targets"], data["reg_loss_mask"], normalizer=self.loss_normalizer)
@@ -86,15 +81,10 @@ class FaFModule(object):
         from .. import tuning
         if tuning.get("TRAIN_HIP") != 1 or tuning.get("TRAIN_GRAPH") != 1:
             return False
-        if hasattr(self.model, "outc"):
+        if hasattr(self.model, "outc"):             # a segmentation variant: SegModule's step
             return False
-        if hasattr(self.model, "convgru"):          # V2VNet: the frame plan is baked into the graph -- only for the agent table it was captured with
-            g = self.optimizer.__dict__.get("_v2x_graphed_steps", {}).get(self._graph_key(data, batch_size))
-            if g is not None and not torch.equal(data["num_agent"].cpu(), g.num_agent):
-                return False
-        elif not hasattr(self.model, "stpn"):       # FaFNet has no per-batch host plan; the other baselines stay eager
-            return False
-        return all(g.get("capturable", True) for g in self.optimizer.param_groups)
+        from ..train.graph_step import cached_step, capture_ok
+        return capture_ok(self.model, self.optimizer, data, cached_step(self.optimizer, self._graph_key(data, batch_size)))
 
     def set_link_mask(self, mask):
         """Late fusion's "who hears whom": (B, A, A) bool, entry [b, i, j] = ego i of frame b receives agent j's boxes; a false diagonal entry
@@ -221,12 +211,7 @@ class FaFModule(object):
 
         def run():
             with torch.no_grad():
-                if hasattr(self.model, "handshake"):
-                    return self.model(bev_seq, data["trans_matrices"], data["num_agent"], training=False, inference=inference,
-                                      batch_size=batch_size)
-                if hasattr(self.model, "fuse"):
-                    return self.model(bev_seq, data["trans_matrices"], data["num_agent"], batch_size=batch_size)
-                return self.model(bev_seq)
+                return self.model.run_batch(data, batch_size, inference)
         dets = None
         late = links = fused = None
         post = self.postprocess

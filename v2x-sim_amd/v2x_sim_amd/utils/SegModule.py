@@ -29,13 +29,12 @@ class SegModule(object):
         if self._graph_ok(data, batch_size):
             # TRAIN_SEG_GRAPH = 1 (with TRAIN_HIP): the whole step as one hipGraph (train/graph_step.py::GraphedSegTrainStep), under FaFModule.step's
             # conditions and caching rule -- the captured steps live on the optimizer, one per batch shape
-            from ..train.graph_step import GraphedSegTrainStep
+            from ..train.graph_step import GraphedSegTrainStep, cached_step
             key = self._graph_key(data, batch_size)
-            cache = self.optimizer.__dict__.setdefault("_v2x_graphed_steps", {})
-            if key not in cache:
-                cache[key] = GraphedSegTrainStep(self.model, self.optimizer, data, batch_size, class_weight=self.class_weight, ignore_index=self.ignore_index)
-            self._graphed = (key, cache[key])
-            return cache[key](data).item()
+            step = cached_step(self.optimizer, key, lambda: GraphedSegTrainStep(self.model, self.optimizer, data, batch_size, class_weight=self.class_weight,
+                                                                                ignore_index=self.ignore_index))
+            self._graphed = (key, step)
+            return step(data).item()
         if tuning.get("TRAIN_HIP") == 1 and tuning.get("TRAIN_SEG_LOSS_HIP") != 0:
             # the eager step with the loss on csrc/seg_loss.hip (and, TRAIN_SEG_HEAD_FUSE, the class head fused with it)
             from ..train.hip_graph import seg_train_loss
@@ -60,32 +59,19 @@ class SegModule(object):
         from .. import tuning
         if tuning.get("TRAIN_HIP") != 1 or tuning.get("TRAIN_SEG_GRAPH") != 1 or self.optimizer is None or not hasattr(self.model, "outc"):
             return False
-        if hasattr(self.model, "convgru"):          # V2VNetSeg: the frame plan is baked into the graph -- only for the agent table it was captured with
-            g = self.optimizer.__dict__.get("_v2x_graphed_steps", {}).get(self._graph_key(data, batch_size))
-            if g is not None and not torch.equal(data["num_agent"].cpu(), g.num_agent):
-                return False
-        elif not hasattr(self.model, "stpn"):       # When2comSeg and the fusion family: no captured step exists for them -- their steps run eager
-            return False                            # (the kernel loss paths of step() still apply)
-        return all(g.get("capturable", True) for g in self.optimizer.param_groups)
+        # (When2comSeg and the fusion family: no captured step exists for them -- their steps run eager, the kernel loss paths of step() still apply)
+        from ..train.graph_step import cached_step, capture_ok
+        return capture_ok(self.model, self.optimizer, data, cached_step(self.optimizer, self._graph_key(data, batch_size)))
 
     def predict(self, data, batch_size=1, label=None, inference=None):
         """-> (pred (A*B, X, Y) uint8, confusion matrix int64 [n_cls, n_cls] or None) on the HIP path.  when2com variants: `inference`
         ('softmax' | 'activated' | 'argmax_test', default 'activated') selects the links, and self.last_num_connect keeps the communication
         rate of this batch (When2com.num_connect)."""
         from .. import ops
-        from ..models.det.FaFNet import FaFNet
-        from ..models.det.When2com import When2com
         self.model.eval()
         with torch.no_grad():
-            x0 = self.model._input_nhwc(data["bev_seq"])
-            if isinstance(self.model, FaFNet):          # lowerbound / upperbound: no exchange
-                logits = self.model.forward_nhwc(x0)
-            elif isinstance(self.model, When2com):
-                logits, _, coef = self.model.forward_nhwc(x0, data["trans_matrices"], data["num_agent"], training=False,
-                                                          inference=inference or "activated", batch_size=batch_size, return_handshake=True)
-                self.last_num_connect = When2com.num_connect(coef, self.model.agent_num)
-            else:                                       # V2VNetSeg and the fusion family
-                logits = self.model.forward_nhwc(x0, data["trans_matrices"], data["num_agent"], batch_size=batch_size)
+            logits = self.model.run_batch(data, batch_size, inference)
+        self.last_num_connect = self.model.last_num_connect
         return ops.seg_argmax_confusion(logits, label)
 
 
