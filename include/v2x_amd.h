@@ -625,6 +625,27 @@ int v2x_det_assign_targets(const float *gt_boxes, const int32_t *gt_count, long 
                            float pos_thr, float neg_thr, int force_match, float *labels, float *reg_targets, uint8_t *reg_loss_mask, int32_t *assoc,
                            float *anchor_iou, float *gt_max_iou, int32_t *gt_best, void *workspace, long long workspace_bytes, v2x_stream_t stream);
 
+/* a8 / f-3: segmentation training targets -- the annotated boxes of every item painted into the per-cell class map bev_seg (upstream's
+ * create_data_seg.py does it when the data is created; DESIGN.md section 3.8 "Box rasterization" is the frozen rule).  All n items of the call in at
+ * most two launches (a workgroup per 16 x 16 tile of cells and item; with hist, a workgroup per item); no global atomics, no allocation, no host
+ * synchronisation, capturable; EVERY output element is written, the caller clears nothing.
+ * boxes fp32 [n][cap][5] (x, y, w, h, yaw), cls uint8 [n][cap], count int32 [n] (clamped to [0, cap]), cap in [1, 256].
+ * Grid: X x Y cells of vx x vy > 0 from the corner (x0, y0); the centre of cell (i, j) is px = x0 + (i + 0.5) * vx, py = y0 + (j + 0.5) * vy.
+ * Coverage: box g covers cell (i, j) iff |lx| <= w/2 and |ly| <= h/2, lx = (px-x)*c + (py-y)*s, ly = -(px-x)*s + (py-y)*c, c = cos(yaw), s = sin(yaw) --
+ *   fp64 from the fp32 inputs in exactly that order, every product and sum rounded on its own; borders are closed.  A box with a non-finite field or a
+ *   negative extent is dropped; a zero extent is valid (such a box covers a centre only if it lies exactly on it).
+ * Winner: among the boxes that cover the cell the greatest rank, the lowest box index on ties.  Class 0 is background and never paints (its boxes are
+ *   no-ops); a class c in [1, n_cls) paints c with rank rank[c], or c itself when rank is NULL (a higher id paints over a lower one); a class >= n_cls
+ *   paints the ignore label 255 and outranks every class.  An uncovered cell is 0.  n_cls in [2, 32]; rank uint8 [n_cls] or NULL.
+ * labels uint8 [n][X][Y] (what v2x_seg_loss_* and v2x_seg_argmax_confusion read); owner int32 [n][X][Y] or NULL: the winning box's index in its item's
+ *   list (dropped boxes keep their places), -1 where none; hist int64 [n][n_cls + 1] or NULL: cells per label, the last column counts 255.
+ * workspace: needed with hist only; DEVICE, 4-byte aligned, workspace_bytes >= v2x_seg_rasterize_workspace_size (-1 for sizes out of range); it needs no
+ *   initialisation.  n * tiles must stay below 2^31.  n == 0: nothing to do (V2X_OK), whatever the other arguments are. */
+long long v2x_seg_rasterize_workspace_size(long long n, int X, int Y, int n_cls);
+int v2x_seg_rasterize(const float *boxes, const uint8_t *cls, const int32_t *count, long long n, int cap, float x0, float y0, float vx, float vy, int X,
+                      int Y, int n_cls, const uint8_t *rank, uint8_t *labels, int32_t *owner, long long *hist, void *workspace,
+                      long long workspace_bytes, v2x_stream_t stream);
+
 /* ---------------------------------------------------------------- f-1: the metric (coperception/utils/mean_ap.py::eval_map)
  * Upstream intersects shapely polygons on the host; here the IoU of rotated boxes (x, y, w, h, yaw) is a convex clip in
  * fp64 on the device.

@@ -5,6 +5,7 @@
     python tools/seg/train_seg.py --data synthetic --com v2v --steps 300 --batch 2 --logpath out/
     python tools/seg/train_seg.py --data /path/V2X-Sim-seg/train --com v2v --nepoch 5 --batch 2 --logpath out/
     python tools/seg/train_seg.py --data synthetic --com when2com --steps 20 --batch 1        (--com: every detection baseline but `late`)
+    python tools/seg/train_seg.py --data synthetic --targets boxes --class_weight balanced    (labels rasterized on the GPU, median-frequency weights)
 
 Synthetic scenes (utils/synthetic_scene.py: vehicle footprints as class 1), PyTorch-ROCm autograd over the HIP engine's
 parameter tree, checkpoint with upstream's 'model_state_dict' key for tools/seg/test_seg.py / eval_seg.py --resume."""
@@ -21,14 +22,72 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-def seg_batch(config, frames, agents, seed, device, grid):
+TARGETS = ("map", "boxes")
+
+
+def seg_batch(config, frames, agents, seed, device, grid, targets="map", n_classes=8):
+    """targets="map": the label maps painted per item on the host (synthetic_scene.seg_labels) and uploaded; "boxes": the padded boxes uploaded and
+    rasterized for the whole batch in one call on the device (train/loop.py::seg_targets_on_device, DESIGN.md section 3.8)."""
     from v2x_sim_amd import ops
     from v2x_sim_amd.utils import synthetic_scene
     b = synthetic_scene.make_batch(frames, agents, seed=seed)
     bits = ops.voxelize_bits(torch.from_numpy(b["points"]).to(device), torch.from_numpy(b["n_pts"]).to(device), grid)
-    labels = np.stack([synthetic_scene.seg_labels(b["gt_boxes"][a][f], config) for a in range(agents) for f in range(frames)])
+    if targets == "boxes":
+        from v2x_sim_amd.train.loop import seg_targets_on_device
+        labels = seg_targets_on_device([b["gt_boxes"][a][f] for a in range(agents) for f in range(frames)], None, config, device, n_classes=n_classes)["labels"]
+    else:
+        labels = torch.from_numpy(np.stack([synthetic_scene.seg_labels(b["gt_boxes"][a][f], config) for a in range(agents) for f in range(frames)])).to(device)
     return {"bev_seq": ops.bits_to_dense(bits, grid.dims[2])[:, None], "trans_matrices": torch.from_numpy(b["trans"]).to(device),
-            "num_agent": torch.from_numpy(b["num_agent"]), "labels": torch.from_numpy(labels).to(device)}
+            "num_agent": torch.from_numpy(b["num_agent"]), "labels": labels}
+
+
+BALANCE_BATCHES = 32     # synthetic data: the class frequencies come from the first 32 batches
+
+
+def synthetic_label_hist(config, frames, agents, first_seed, device, n_classes):
+    """Cells per class over the first BALANCE_BATCHES synthetic batches of a run, from the rasterizer's histogram (only the boxes are uploaded)."""
+    from v2x_sim_amd.train.loop import seg_targets_on_device
+    from v2x_sim_amd.utils import synthetic_scene
+    total = torch.zeros((n_classes + 1,), dtype=torch.int64, device=device)
+    for it in range(BALANCE_BATCHES):
+        b = synthetic_scene.make_batch(frames, agents, seed=first_seed + it)
+        res = seg_targets_on_device([b["gt_boxes"][a][f] for a in range(agents) for f in range(frames)], None, config, device, n_classes=n_classes,
+                                    want=("hist",))
+        total += res["hist"].sum(0)
+    return total.cpu().numpy()
+
+
+def dataset_label_hist(dataset, grid, device, n_classes):
+    """Cells per class over ONE pass of a parsed set: bev_seg maps are counted with torch.bincount on the device, boxes samples through the
+    rasterizer's histogram, a frame's agents in one call."""
+    from v2x_sim_amd import ops
+    total = torch.zeros((n_classes + 1,), dtype=torch.int64, device=device)
+    for k in range(len(dataset)):
+        labels = [t[1] for t in dataset[k]]
+        kinds = [isinstance(lab, tuple) for lab in labels]
+        if any(kinds) and not all(kinds):
+            raise ValueError("frame %d mixes bev_seg samples and gt_boxes samples" % k)
+        if kinds[0]:
+            boxes, cls, count = ops.pad_box_lists([lab[0] for lab in labels], [lab[1] for lab in labels])
+            res = ops.rasterize_seg(torch.from_numpy(boxes).to(device), torch.from_numpy(cls).to(device), torch.from_numpy(count).to(device), grid,
+                                    n_classes=n_classes, want=("hist",))
+            total += res["hist"].sum(0)
+        else:
+            seen = torch.bincount(torch.from_numpy(np.stack(labels)).to(device).reshape(-1).long(), minlength=256)
+            total[:n_classes] += seen[:n_classes]
+            total[n_classes] += seen[n_classes:].sum()
+    return total.cpu().numpy()
+
+
+def class_weight_arg(text):
+    """--class_weight: '' (none), 'balanced', or a comma list of floats (kept as text; main() parses it)."""
+    if text in ("", "balanced"):
+        return text
+    try:
+        [float(v) for v in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected `balanced` or a comma list of numbers, got %r" % text)
+    return text
 
 
 def build_parser():
@@ -54,7 +113,13 @@ def build_parser():
                          "as PyTorch ops; hip-graph = the same with the loss kernels, the class head fused with the loss and every step replayed as one hipGraph "
                          "(V2X_TRAIN_SEG_LOSS_HIP / _HEAD_FUSE / _GRAPH = 1; a capturable Adam with a device-tensor learning rate).  Default: whatever the "
                          "environment variables say")
-    ap.add_argument("--class_weight", default="", type=str, help="comma list of per-class loss weights (the kernel loss paths; default: none)")
+    ap.add_argument("--class_weight", default="", type=class_weight_arg,
+                    help="comma list of per-class loss weights (the kernel loss paths; default: none), or `balanced`: median-frequency weights "
+                         "w_c = median(f) / f_c over the classes that occur (0 for the absent ones), computed before training -- synthetic data: from the "
+                         "first 32 batches; a parsed set: from one pass over it")
+    ap.add_argument("--targets", default="map", choices=list(TARGETS),
+                    help="synthetic data: map = label maps painted per item on the host and uploaded; boxes = the boxes uploaded and rasterized for the whole "
+                         "batch in one call on the GPU (v2x_seg_rasterize).  A parsed set decides per sample: bev_seg maps or gt_boxes + gt_classes")
     return ap
 
 
@@ -65,7 +130,7 @@ def main(argv=None):
         tuning.set("TRAIN_HIP", int("0" if args.engine == "torch" else "1"))
         for name in ("TRAIN_SEG_LOSS_HIP", "TRAIN_SEG_HEAD_FUSE", "TRAIN_SEG_GRAPH"):
             tuning.set(name, int("1" if args.engine == "hip-graph" else "0"))
-    class_weight = [float(v) for v in args.class_weight.split(",")] if args.class_weight else None
+    class_weight = [float(v) for v in args.class_weight.split(",")] if args.class_weight not in ("", "balanced") else None
     from v2x_sim_amd import ops
     from v2x_sim_amd.configs import Config
     from v2x_sim_amd.models.seg import COM_CLASSES, When2comSeg, default_inference
@@ -112,17 +177,24 @@ def main(argv=None):
         start = int(ckpt["epoch"]) + 1
     if class_weight is not None and len(class_weight) != model.n_classes:
         raise SystemExit("--class_weight needs %d values" % model.n_classes)
-    module = SegModule(model, None, config, opt, 0, class_weight=class_weight)
     grid = ops.VoxelGrid(config.voxel_size, config.area_extents)
+    if args.class_weight == "balanced":
+        if loader is not None:
+            hist = dataset_label_hist(dataset, grid, device, model.n_classes)
+        else:
+            hist = synthetic_label_hist(config, args.batch, A, (args.seed + start) * 1000003, device, model.n_classes)
+        class_weight = ops.median_frequency_weights(hist, model.n_classes)
+        print("class weights (median frequency): %s" % ", ".join("%.4g" % w for w in class_weight))
+    module = SegModule(model, None, config, opt, 0, class_weight=class_weight)
     for epoch in range(start, args.nepoch + 1):
         losses, last = [], None
         if loader is not None:
             for samples in loader:
-                last = (seg_batch_on_device(samples, grid, device), len(samples))
+                last = (seg_batch_on_device(samples, grid, device, n_classes=model.n_classes), len(samples))
                 losses.append(module.step(last[0], len(samples[0]), len(samples)))
         else:
             for it in range(args.steps):
-                last = (seg_batch(config, args.batch, A, (args.seed + epoch) * 1000003 + it, device, grid), args.batch)
+                last = (seg_batch(config, args.batch, A, (args.seed + epoch) * 1000003 + it, device, grid, args.targets, model.n_classes), args.batch)
                 losses.append(module.step(last[0], A, args.batch))
                 if args.log and it % 20 == 0:
                     print("step %4d  loss %.4f" % (it, losses[-1]), flush=True)

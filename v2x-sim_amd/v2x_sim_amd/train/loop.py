@@ -54,6 +54,18 @@ def iou_targets_on_device(gt_lists, anchors, device, **assign_kw):
     return res["labels"], res["reg_targets"], res["reg_loss_mask"].view(torch.bool)
 
 
+def seg_targets_on_device(box_lists, class_lists, config, device, n_classes=8, rank=None, want=(), out=None):
+    """The segmentation labels of DESIGN.md section 3.8's rule for a batch, the twin of iou_targets_on_device: box_lists = one (G_m, 5) array of boxes
+    per item, in the models' batch order, class_lists = one (G_m,) array of class ids per item (None: every box is class 1); padded to the longest
+    list, uploaded once and rasterized in ONE call (ops.rasterize_seg) on config's grid -- no per-item work on the host.  rank: a host sequence of
+    n_classes ranks or None.  -> ops.rasterize_seg's dict: labels (n, X, Y) uint8 on the device and whatever `want` names (owner, hist)."""
+    import numpy as np
+    boxes, cls, count = ops.pad_box_lists(box_lists, class_lists)
+    d_rank = None if rank is None else torch.from_numpy(np.asarray(rank, np.uint8).reshape(-1)).to(device)
+    return ops.rasterize_seg(torch.from_numpy(boxes).to(device), torch.from_numpy(cls).to(device), torch.from_numpy(count).to(device), config,
+                             n_classes=n_classes, rank=d_rank, want=want, out=out)
+
+
 def synthetic_batch_on_device(config, frames, agents, seed, device, grid=None, anchors=None, with_targets=True, targets="radius", **scene_kw):
     """-> data dict in FaFModule.step / predict_all's format (+ 'gt_boxes'[agent][frame] host arrays).
     targets: the assignment rule -- "radius": positives built per item on the host and scattered on the device; "iou": the

@@ -43,7 +43,8 @@ class SegModule(object):
                                   ignore_index=self.ignore_index)
         else:
             logits = train_forward(self.model, bev, data.get("trans_matrices"), data.get("num_agent"), batch_size)
-            loss = F.cross_entropy(logits.reshape(-1, logits.shape[-1]), data["labels"].reshape(-1).long())
+            # (ignore_index: a rasterized map may hold the ignore label; without it a 255 is an out-of-range target.  Maps without one: the same bits)
+            loss = F.cross_entropy(logits.reshape(-1, logits.shape[-1]), data["labels"].reshape(-1).long(), ignore_index=self.ignore_index)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.optimizer.step()
