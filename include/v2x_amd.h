@@ -390,6 +390,28 @@ int v2x_warp_fuse_ordered(const uint16_t *feat, int A, int Bt, int H, int W, int
                           const float *coef, int mode, uint16_t *out, const int32_t *order, int order_stride, int order_len,
                           v2x_stream_t stream);
 
+/* Degraded links (row f-4; DESIGN.md section 3.9 is the frozen rule): this step's fusion plan and poses from the static plan and the clean poses, in
+ * ONE launch (one workgroup; no allocation, no host synchronisation, capturable).  p_outage: every directed link j -> i (j != i) is down with that
+ * probability, independently; pose_sigma: Gaussian noise of that many metres on the translation of every agent-to-agent transform.
+ * Generator: Philox4x32-10.  For the directed pair (ego i, source j) of frame f at step s:
+ *   w[0..3] = philox(counter = (s & 0xffffffff, s >> 32, f, (domain << 16) | (i << 8) | j), key = (seed & 0xffffffff, seed >> 32)), A <= 32.
+ *   Outage (domain 0): u = float(w[0] >> 8) * 2^-24; the link is down iff u < p_outage.  coef[m][j] = coef0[m][j] for j == ego(m) and for a link
+ *     that is not down, 0 otherwise.  p_outage == 0: nothing is drawn, coef = coef0.
+ *   Pose (domain 1): u_k = (float(w[k] >> 9) + 0.5) * 2^-23; nx = sqrt(-2 ln u_0) cos(2 pi u_1), ny = sqrt(-2 ln u_0) sin(2 pi u_1),
+ *     nz = sqrt(-2 ln u_2) cos(2 pi u_3) in fp32 (libm forms); entries [0][3], [1][3], [2][3] of trans[f][i][j], j != i, become t + pose_sigma * n,
+ *     every other entry and the diagonal pairs are copied.  (v2x_warp_fuse reads [0][3] and [1][3].)
+ * items int32 [n_out][2] = (ego, frame) as for v2x_warp_fuse; an item outside [0, A) x [0, Bt) keeps its static row and draws nothing.
+ * coef0 fp32 [n_out][A]: the static plan's rows, only read.  coef fp32 [n_out][A]: this step's rows.  Both NULL: pose noise alone (p_outage == 0).
+ * coef2 fp32 [n_out * A][A] or NULL: DiscoNet's one-hot rows, coef2[m * A + k][j] = (j == k) ? coef[m][k] : 0.
+ * link uint8 [Bt][A][A] or NULL: link[f][i][j] = 1 iff j != i and coef[m(i, f)][j] != 0; absent egos and the diagonal are 0.
+ * trans fp32 [Bt][A][A][4][4], only read; trans_out the same shape, NULL if and only if pose_sigma == 0 (then trans is not read and may be NULL).
+ * step_dev: DEVICE uint64, 8-byte aligned: read as s by every thread, left as s + 1 by the launch's last statement behind a workgroup barrier.
+ * Every output element is written.  n_out == 0: nothing to do (V2X_OK), whatever the other arguments are.  p_outage outside [0, 1], pose_sigma
+ * negative or not finite, A > 32: V2X_EINVAL. */
+int v2x_channel_degrade(const int32_t *items, int n_out, int A, int Bt, const float *coef0, float *coef, float *coef2, uint8_t *link,
+                        const float *trans, float *trans_out, float p_outage, float pose_sigma, uint64_t seed, uint64_t *step_dev,
+                        v2x_stream_t stream);
+
 /* ---------------------------------------------------------------- a5: attention handshake
  * Replaces When2com.py::MIMOGeneralDotProductAttention (query projection, key.query
  * scores, softmax over the keys) and the inference-time selection

@@ -10,7 +10,14 @@ keeps in its checkpoints; every other flag is test_codet.py's own (v2x_sim_amd/u
 
 --com late is upstream's late fusion (the table's "Co-lower-bound"): test_codet.py runs as --com lowerbound, the FaFModule it builds exchanges the
 agents' detections and suppresses the union per ego (FaFModule.late_fusion; --only_v2i masks the links), and the share of the kept boxes that
-came from neighbours is printed after the scores."""
+came from neighbours is printed after the scores.
+
+    python tools/det/eval_codet.py --data /path/V2X-Sim-det/test --com v2v --resume ckpt.pth --p_com_outage 0.3 --pose_noise 0.5 [--channel_seed 7]
+
+--p_com_outage p (every directed link down with probability p at every step) and --pose_noise sigma (Gaussian noise, metres, on the translation of the
+agent-to-agent transforms) are drawn on the device from (--channel_seed, step).  They are an evaluation condition: no checkpoint
+records them; --com lowerbound / upperbound / late refuse them, when2com / who2com take --pose_noise only.  The realised share of links up is printed
+after the scores."""
 import os
 import sys
 

@@ -65,6 +65,7 @@ def main(argv=None):
         raise SystemExit("train_codet.py needs the MI355X")
     config = Config("train", binary=True, only_det=True)
     A = args.num_agent
+    comm.refuse_channel_in_training(args)
     ckw = comm.model_kwargs(args, intermediate=args.com not in ("lowerbound", "upperbound"))
     if args.com == "v2v":
         model = V2VNet(config, gnn_iter_times=args.gnn_iter_times, layer=args.layer, num_agent=A, **ckw)

@@ -9,7 +9,10 @@
 (softmax | activated | argmax_test; default 'activated', who2com -- a When2comSeg, as in tools/det/test_codet.py -- 'argmax_test').
 Either way --compress_level k (0..8) and --only_v2i 0|1 reach the model's constructor through comm.model_flags and are checked against the record
 tools/seg/train_seg.py keeps in its checkpoints (v2x_sim_amd/utils/comm.py::run_eval_driver).  when2com takes --compress_level; under
---only_v2i 1 the When2comSeg constructor raises its NotImplementedError (when2com has no agreed reading under a link mask)."""
+--only_v2i 1 the When2comSeg constructor raises its NotImplementedError (when2com has no agreed reading under a link mask).
+--p_com_outage p, --pose_noise sigma and --channel_seed s (degraded links drawn on the device) travel the same way but are an
+evaluation condition: no checkpoint records them, --com lowerbound / upperbound refuse them, when2com / who2com take --pose_noise only; the realised
+share of links up is printed after the IoUs."""
 import argparse
 import os
 import sys

@@ -142,6 +142,7 @@ def main(argv=None):
     device = torch.device("cuda:0")
     config = Config("train", binary=True, only_det=True)
     A = args.num_agent
+    comm.refuse_channel_in_training(args)
     ckw = comm.model_kwargs(args, intermediate=args.com not in ("lowerbound", "upperbound"))
     model = COM_CLASSES[args.com](config, num_agent=A, **ckw)
     if args.engine == "hip-graph" and args.com not in ("lowerbound", "upperbound", "v2v"):

@@ -88,9 +88,11 @@ class V2VNet(IntermediateModelBase):
                 raise RuntimeError("V2VNet needs >= 1 linked neighbour for every ego (stack expects a non-empty TensorList): "
                                    "agent %d of frame %d has none under the link mask" % (a, f))
         full = len(items) == A * batch_size
-        return {"items": ops.items_tensor(items, A, batch_size, device),
-                "coef": coef.to(device), "rows": None if full else torch.tensor(rows, device=device),
-                "n_items": len(items)}
+        # (a degraded model: the static rule above stays; an ego whose links are all DOWN BY OUTAGE has the empty neighbour list -- its mean message
+        # is the zero map, which every form of the warp kernel writes for a count of 0, and the ConvGRU runs on it: DESIGN.md section 3.9)
+        return self.channel_plan({"items": ops.items_tensor(items, A, batch_size, device),
+                                  "coef": coef.to(device), "rows": None if full else torch.tensor(rows, device=device),
+                                  "n_items": len(items)}, batch_size, device)
 
     def fuse(self, feat, trans_matrices, plan, batch_size, pk):
         """feat: (A*B, H, W, C) bf16 fusion-layer maps, agent-major -> updated maps, same shape."""
@@ -117,6 +119,7 @@ class V2VNet(IntermediateModelBase):
         feats = LidarEncoder.run(pk["enc"], x0, zbits=zbits)
         if plan is None:
             plan = self.make_plan(num_agent_tensor, batch_size, x0.device)
+        plan, trans_matrices = self.degrade(plan, trans_matrices)
         feats[self.layer] = self.fuse(feats[self.layer], trans_matrices, plan, batch_size, pk)
         return self.head(pk, feats)
 

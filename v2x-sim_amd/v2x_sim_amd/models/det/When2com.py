@@ -107,6 +107,7 @@ class MIMOGeneralDotProductAttention(_ParamsOnly):
 
 class When2com(IntermediateModelBase):
     FAMILY = "when2com"
+    CHANNEL_OUTAGE = False       # pose noise only: link outage has no agreed reading for the attention, like a link mask
 
     def __init__(self, config, n_classes=21, in_channels=13, feat_channel=512, feat_squeezer=-1,
                  attention="additive", has_query=True, sparse=False, layer=3, warp_flag=1, image_size=512,
@@ -168,9 +169,9 @@ class When2com(IntermediateModelBase):
             mask[m, :counts[f]] = 1.0
         full = len(items) == A * batch_size
         it = torch.tensor(items, dtype=torch.int64)
-        return {"items": ops.items_tensor(items, A, batch_size, device), "mask": mask.to(device),
-                "rows": None if full else torch.tensor(rows, device=device),
-                "q_idx": it[:, 0].to(device), "f_idx": it[:, 1].to(device)}
+        return self.channel_plan({"items": ops.items_tensor(items, A, batch_size, device), "mask": mask.to(device),
+                                  "rows": None if full else torch.tensor(rows, device=device),
+                                  "q_idx": it[:, 0].to(device), "f_idx": it[:, 1].to(device)}, batch_size, device, coef=None)
 
     def handshake(self, x0, pk, batch_size, mode):
         """Policy tower + key/query MLPs + attention scores.  -> prob, coef (B, A_key, A_query)."""
@@ -191,6 +192,7 @@ class When2com(IntermediateModelBase):
         feats = LidarEncoder.run(pk["enc"], x0)
         if plan is None:
             plan = self.make_plan(num_agent_tensor, batch_size, x0.device)
+        plan, trans_matrices = self.degrade(plan, trans_matrices)
         if training or inference == "softmax":
             mode = "softmax"
         elif inference in ("activated", "argmax_test"):

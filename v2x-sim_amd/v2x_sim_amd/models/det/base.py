@@ -359,17 +359,26 @@ class IntermediateModelBase(DetModelBase):
     def __init__(self, config, layer=3, in_channels=13, kd_flag=True, p_com_outage=0.0, num_agent=5,
                  compress_level=0, only_v2i=False):
         super().__init__(config, layer, in_channels, kd_flag, p_com_outage, num_agent, only_v2i)
-        if p_com_outage != 0.0:
-            raise NotImplementedError("p_com_outage is out of scope (DESIGN.md s9)")
         from ...utils import comm
         flags = comm.current_model_flags()      # inside `with comm.model_flags(...)`: what a constructor call that leaves the two at their defaults takes
+        pose_noise, channel_seed = 0.0, 0
         if flags is not None:
             if compress_level == 0:
                 compress_level = flags["compress_level"]
             only_v2i = only_v2i or flags["only_v2i"]
+            if p_com_outage == 0.0:
+                p_com_outage = flags.get("p_com_outage", 0.0)
+            pose_noise, channel_seed = flags.get("pose_noise", 0.0), flags.get("channel_seed", 0)
         self.compress_level = compress_level
         self.only_v2i = bool(only_v2i)
         self._link_mask = None
+        # the degraded-link condition: what the next make_plan() takes, the step counter (device memory once a plan exists) and the last draw
+        self._channel = None
+        self._channel_step0, self._channel_step, self._last_links, self._channel_stats = 0, None, None, None
+        self.set_channel(p_com_outage, pose_noise, channel_seed)
+        if flags is not None and "channel_models" in flags and self._channel is not None:
+            flags["channel_models"].append(self)       # the evaluation tools print the realised share of links up (comm.run_eval_driver)
+            self._channel_stats = [None, None]
         self.u_encoder = LidarEncoder(in_channels, compress_level=compress_level)
         self.decoder = LidarDecoder(in_channels)
 
@@ -402,6 +411,108 @@ class IntermediateModelBase(DetModelBase):
             mb = None if m is None else (m if m.dim() == 2 else m[b]).tolist()
             out.append([[(mb is None or bool(mb[i][j])) and (not self.only_v2i or i == 0 or j == 0) for j in range(A)] for i in range(A)])
         return out
+
+    # ---- degraded links: p_com_outage and pose noise drawn on the device --------------------------------
+    CHANNEL_OUTAGE = True          # False: the family takes pose noise only (when2com: its attention has no agreed reading under a link mask)
+
+    def set_channel(self, p_com_outage=0.0, pose_noise=0.0, seed=0):
+        """Every directed link j -> i is down with probability p_com_outage at every step, independently; pose_noise is the sigma in metres of Gaussian
+        noise on the translation of every agent-to-agent transform; seed (64 bits) keys the counter-based generator, so a host predicts every draw
+        from (seed, step).  Like set_link_mask it takes effect in the next make_plan(): a plan built before keeps its condition."""
+        import math
+        p, sigma = float(p_com_outage), float(pose_noise)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("p_com_outage must lie in [0, 1], got %r" % (p_com_outage,))
+        if not (sigma >= 0.0 and math.isfinite(sigma)):
+            raise ValueError("pose_noise must be finite and >= 0, got %r" % (pose_noise,))
+        seed = int(seed)
+        if not 0 <= seed < (1 << 64):
+            raise ValueError("the channel seed must lie in [0, 2^64), got %r" % (seed,))
+        if p > 0.0 and not self.CHANNEL_OUTAGE:
+            raise NotImplementedError("when2com under link outage is out of scope: its attention has no agreed reading under a link mask "
+                                      "(DESIGN.md section 9); pose noise alone is accepted")
+        self._channel = None if (p == 0.0 and sigma == 0.0) else (p, sigma, seed)
+
+    @property
+    def p_com_outage(self):
+        return 0.0 if self._channel is None else self._channel[0]
+
+    @property
+    def pose_noise(self):
+        return 0.0 if self._channel is None else self._channel[1]
+
+    def reset_channel(self, step=0):
+        """The step counter := step (stream-ordered, no synchronisation): the next degraded forward draws the links and the noise of that step."""
+        step = int(step)
+        if not 0 <= step < (1 << 63):
+            raise ValueError("the channel step must lie in [0, 2^63), got %r" % (step,))
+        self._channel_step0 = step
+        if self._channel_step is not None:
+            self._channel_step.fill_(step)
+
+    def channel_step(self):
+        """The step the next degraded forward will draw.  The ONLY call of the feature that synchronises with the host."""
+        return self._channel_step0 if self._channel_step is None else int(self._channel_step.item())
+
+    def last_links(self):
+        """(B, A, A) uint8 device tensor of the last draw: [f][i][j] = 1 iff ego i of frame f fused source j != i; None before the first one and
+        under pose noise alone."""
+        return self._last_links
+
+    def _channel_counter(self, device):
+        if self._channel_step is None or self._channel_step.device != torch.device(device):
+            self._channel_step = torch.tensor([self._channel_step0], dtype=torch.int64, device=device)    # the kernel reads it as a uint64
+        return self._channel_step
+
+    def channel_plan(self, plan, batch_size, device, coef="coef", coef2=None, also=()):
+        """What every family's make_plan() ends in.  Undegraded: the plan as it is.  Degraded: one more entry, "channel" -- the static rows, the live
+        buffers of this step's rows (and DiscoNet's one-hot rows), the link table and the pose buffer: allocated ONCE here, so their addresses are
+        stable under capture.  Every other entry of the plan stays what the family built."""
+        if self._channel is None:
+            return plan
+        p, sigma, seed = self._channel
+        A = self.agent_num
+        ch = {"p": p, "sigma": sigma, "seed": seed, "Bt": batch_size, "coef0": None, "coef": None, "coef2": None, "links": None,
+              "trans": torch.empty((batch_size, A, A, 4, 4), dtype=torch.float32, device=device) if sigma > 0.0 else None}
+        live = dict(plan)
+        if coef is not None:
+            c0 = plan[coef].contiguous()
+            ch["coef0"], ch["coef"] = c0, torch.empty_like(c0)
+            ch["links"] = torch.zeros((batch_size, A, A), dtype=torch.uint8, device=device)
+            live[coef] = ch["coef"]
+            for k in also:                       # DiscoNet's `valid` = coef
+                live[k] = ch["coef"]
+            if coef2 is not None:
+                ch["coef2"] = torch.empty_like(plan[coef2])
+                live[coef2] = ch["coef2"]
+            eye = torch.eye(A, device=c0.device).index_select(0, plan["items"][:, 0].long().to(c0.device))
+            ch["possible"] = ((c0 != 0) & (eye == 0)).sum()          # the static plan's links: what the realised share is measured against
+        ch["live"] = live
+        self._channel_counter(plan["items"].device)
+        plan = dict(plan)
+        plan["channel"] = ch
+        return plan
+
+    def degrade(self, plan, trans_matrices):
+        """-> (this step's plan, this step's poses): ONE ops.channel_degrade launch on a degraded plan, the arguments themselves otherwise."""
+        ch = plan.get("channel")
+        if ch is None:
+            return plan, trans_matrices
+        trans = trans_matrices.to(torch.float32).contiguous() if ch["trans"] is not None else None
+        ops.channel_degrade(plan["items"], self.agent_num, ch["Bt"], ch["coef0"], ch["coef"], ch["coef2"], ch["links"], trans, ch["trans"],
+                            ch["p"], ch["sigma"], ch["seed"], self._channel_counter(plan["items"].device))
+        self._last_links = ch["links"]
+        if self._channel_stats is not None and ch["links"] is not None:       # built by an evaluation tool: device-side sums, read once at the end
+            up, possible = ch["links"].sum(), ch["possible"]
+            self._channel_stats = [up if self._channel_stats[0] is None else self._channel_stats[0] + up,
+                                   possible if self._channel_stats[1] is None else self._channel_stats[1] + possible]
+        return ch["live"], (ch["trans"] if ch["trans"] is not None else trans_matrices)
+
+    def channel_link_stats(self):
+        """-> (links up, links the static plans allowed) summed over the degraded forwards so far (synchronises); (0, 0) where nothing was counted."""
+        if not self._channel_stats or self._channel_stats[0] is None:
+            return 0, 0
+        return int(self._channel_stats[0].item()), int(self._channel_stats[1].item())
 
     def fusion_shape(self):
         return LAYER_SHAPES[self.layer]

@@ -2,7 +2,7 @@
 {SumFusion,MeanFusion,MaxFusion,CatFusion}.py on base/FusionBase.py (absent from /root/reference; README.md:101 lists
 the benchmark family).  Per ego agent: the ego map and every neighbour's map warped into the ego frame are reduced by
 sum / mean / max; CatFusion concatenates the ego map with that mean and applies a 1x1 conv + BN + ReLU
-(ModulationLayer3).  From recollection upstream's list STARTS with the ego map; frozen here (DESIGN.md section 3.9).
+(ModulationLayer3).  From recollection upstream's list STARTS with the ego map; frozen here (DESIGN.md section 3).
 
 MI355X mapping: the whole reduction is ONE warp_fuse launch (modes WSUM with unit coefficients / MEAN / MAX; the ego
 term is read unwarped), and CatFusion's concat is the two-source loader of the 1x1 implicit-GEMM layer.
@@ -38,8 +38,12 @@ class FusionBase(IntermediateModelBase):
                     if j != a and not L[f][a][j]:
                         coef[m, j] = 0.0
         full = len(items) == A * batch_size
-        return {"items": ops.items_tensor(items, A, batch_size, device), "coef": coef.to(device),
+        plan = {"items": ops.items_tensor(items, A, batch_size, device), "coef": coef.to(device),
                 "rows": None if full else torch.tensor(rows, device=device)}
+        return self._finish_plan(plan, batch_size, device)
+
+    def _finish_plan(self, plan, batch_size, device):
+        return self.channel_plan(plan, batch_size, device)
 
     def post_fusion(self, ego, fused, pk):
         return fused
@@ -62,6 +66,7 @@ class FusionBase(IntermediateModelBase):
         feats = LidarEncoder.run(pk["enc"], x0)
         if plan is None:
             plan = self.make_plan(num_agent_tensor, batch_size, x0.device)
+        plan, trans_matrices = self.degrade(plan, trans_matrices)
         feats[self.layer] = self.fuse(feats[self.layer], trans_matrices, plan, batch_size, pk)
         return self.head(pk, feats)
 
@@ -155,7 +160,10 @@ class DiscoNet(FusionBase):
         valid = plan["coef"]                                               # (n, A): 1 for real agents
         plan["coef2"] = (torch.eye(A, device=device).repeat(n, 1) * valid.repeat_interleave(A, 0)).contiguous()
         plan["valid"] = valid.contiguous()
-        return plan
+        return self.channel_plan(plan, batch_size, device, coef2="coef2", also=("valid",))
+
+    def _finish_plan(self, plan, batch_size, device):
+        return plan                      # the condition is attached once the one-hot rows exist (make_plan above)
 
     def fuse(self, feat, trans_matrices, plan, batch_size, pk):
         A = self.agent_num

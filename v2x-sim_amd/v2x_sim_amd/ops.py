@@ -481,6 +481,31 @@ def warp_fuse(feat, A, Bt, trans, items, coef, mode, out=None):
     return out
 
 
+def channel_degrade(items, A, Bt, coef0, coef, coef2, link, trans, trans_out, p_outage, pose_sigma, seed, step):
+    """This step's fusion plan and poses from the static plan and the clean poses (DESIGN.md section 3.9), one launch: items (n_out, 2) int32;
+    coef0 -> coef (n_out, A) fp32 (both None: pose noise alone); coef2 (n_out*A, A) fp32 or None; link (Bt, A, A) uint8 or None; trans ->
+    trans_out (Bt, A, A, 4, 4) fp32 (trans_out None if and only if pose_sigma == 0); step: a one-element int64 / uint64 device tensor, read as the
+    step s and left as s + 1.  Nothing synchronises with the host."""
+    n_out = items.shape[0]
+    if coef0 is not None and (tuple(coef0.shape) != (n_out, A) or tuple(coef.shape) != (n_out, A)):
+        raise ValueError("coef0 and coef must be (n_out, A)")
+    if coef2 is not None and tuple(coef2.shape) != (n_out * A, A):
+        raise ValueError("coef2 must be (n_out * A, A)")
+    if link is not None and tuple(link.shape) != (Bt, A, A):
+        raise ValueError("link must be (Bt, A, A)")
+    if trans_out is not None and (trans is None or tuple(trans.shape) != (Bt, A, A, 4, 4) or tuple(trans_out.shape) != (Bt, A, A, 4, 4)):
+        raise ValueError("trans and trans_out must be (Bt, A, A, 4, 4)")
+    if step.numel() != 1 or step.dtype not in (torch.int64, torch.uint64):
+        raise ValueError("step must be one 64-bit integer in device memory")
+    prof = _Prof("channel_degrade_kernel", 0, (2 * n_out * A + (n_out * A * A if coef2 is not None else 0)) * 4 + (2 * Bt * A * A * 64 if trans_out is not None else 0))
+    rc = _lib.load().v2x_channel_degrade(_dev(items, torch.int32, "items"), n_out, A, Bt, _dev_opt(coef0, torch.float32, "coef0"), _dev_opt(coef, torch.float32, "coef"),
+                                         _dev_opt(coef2, torch.float32, "coef2"), _dev_opt(link, torch.uint8, "link"),
+                                         _dev_opt(trans if trans_out is not None else None, torch.float32, "trans"), _dev_opt(trans_out, torch.float32, "trans_out"),
+                                         C.c_float(p_outage), C.c_float(pose_sigma), C.c_uint64(seed), _dev(step, step.dtype, "step"), _stream())
+    prof.done()
+    _lib.check(rc, "v2x_channel_degrade")
+
+
 def items_tensor(items, A, Bt, device):
     """(n_out, 2) int32 device tensor of the (ego, frame) pairs of a fusion plan, with the frame-ordered table v2x_warp_fuse_ordered walks
     attached (built here on the host, where the list is: no device round trip later)."""

@@ -130,6 +130,14 @@ def sparse_exchange(local, full, plan, rank, per_rank, group=None):
     return dist.batch_isend_irecv(ops_) if ops_ else []
 
 
+def _refuse_degraded(model):
+    """The sharded runners build their own fusion plans and exchange maps by them: a model under link outage or pose noise
+    is refused, never run without its condition."""
+    if getattr(model, "p_com_outage", 0.0) or getattr(model, "pose_noise", 0.0):
+        raise NotImplementedError("the sharded runners do not draw degraded links (DESIGN.md section 9): p_com_outage = %g, pose_noise = %g; run the "
+                                  "plain model, or set_channel() back to zero" % (model.p_com_outage, model.pose_noise))
+
+
 class ShardedV2VNet:
     """Runs a v2x_sim_amd V2VNet over this rank's shard.  `exchange` is injectable so that a
     single GPU can emulate R ranks in the equivalence test."""
@@ -137,6 +145,7 @@ class ShardedV2VNet:
     def __init__(self, model, shard, exchange=None, group=None, transport="allgather"):
         if transport not in ("allgather", "needed"):
             raise ValueError("transport must be 'allgather' or 'needed'")
+        _refuse_degraded(model)
         self.model, self.shard, self.group, self.transport = model, shard, group, transport
         self._custom_exchange = exchange is not None
         self.exchange = exchange or (lambda t: exchange_features(t, shard.world, group))
@@ -288,6 +297,7 @@ class ShardedWhen2com:
     def __init__(self, model, shard, exchange=None, group=None, transport="sparse"):
         if transport not in ("allgather", "sparse"):
             raise ValueError("transport must be 'allgather' or 'sparse'")
+        _refuse_degraded(model)
         self.model, self.shard, self.group, self.transport = model, shard, group, transport
         self._custom_exchange = exchange is not None
         self.exchange = exchange or (lambda t: exchange_features(t, shard.world, group))

@@ -370,11 +370,20 @@ def _fusion_stage(model, x, feats, trans_matrices, num_agent_tensor, batch_size,
     return extras
 
 
+def refuse_outage(model):
+    """Link outage is an evaluation condition (DESIGN.md sections 3.9 and 9): a training step of a model with p_com_outage > 0 is refused on either
+    engine, never run without it.  (Pose noise in training needs nothing from the model: noise the pose tensor before the step.)"""
+    if getattr(model, "p_com_outage", 0.0):
+        raise NotImplementedError("training under link outage is out of scope (DESIGN.md section 9): p_com_outage = %g is an evaluation condition; "
+                                  "set_channel(p_com_outage=0) before a training step" % model.p_com_outage)
+
+
 def train_forward(model, bevs, trans_matrices=None, num_agent_tensor=None, batch_size=1, inference="softmax"):
     """bevs (A*B, 1, X, Y, Z) dense occupancy (the Dataset format) -> {'loc', 'cls'} with the shapes of the HIP path (+ when2com's
     'prob_action' / 'coef'); a segmentation variant (a model with the `outc` class head): NHWC fp32 logits.
     Uses batch-statistics BN when model.training, running statistics otherwise.
     V2X_TRAIN_HIP=1: in train mode encoder, decoder and heads run as the bf16 NHWC graph on the hand-written kernels (train/hip_graph.py)."""
+    refuse_outage(model)
     if tuning.get("TRAIN_HIP") == 1 and model.training and bevs.is_cuda:
         from . import hip_graph
         return hip_graph.train_forward(model, bevs, trans_matrices, num_agent_tensor, batch_size, inference)

@@ -800,6 +800,7 @@ def train_forward(model, bevs, trans_matrices=None, num_agent_tensor=None, batch
     train/graph.py::train_forward.  Every detection / segmentation baseline: encoder, decoder and heads on the kernels; the cross-agent
     fusion (V2VNet's warp + ConvGRU, when2com's handshake, sum / mean / max / cat / DiscoNet) on the fp32 graph at the fusion layer.
     model.training must be on."""
+    graph.refuse_outage(model)
     with _forward_scope():
         y, extras = _decoder_output(model, bevs, trans_matrices, num_agent_tensor, batch_size, inference)
         if hasattr(model, "outc"):
