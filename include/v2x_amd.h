@@ -482,6 +482,22 @@ int v2x_det_loss_forward(const float *cls, const float *labels, const float *loc
 int v2x_det_loss_backward(const float *cls, const float *labels, const float *loc, const float *targets, const uint8_t *mask, long long n_anchors,
                           float alpha, float beta, const float *out4, const float *g_loss, const float *g_cls, const float *g_loc, float *dcls,
                           float *dloc, v2x_stream_t stream);
+/* Row f-3, the same loss with the CORNER form of the localisation term (coperception/utils/CoDetModule.py::FaFModule.loss_calculator under
+ * config.loss_type = "corner_loss" -- not in /root/reference; DESIGN.md section 3.10 is the build-owned specification, restated in
+ * v2x_sim_amd/train/loss.py::detection_loss and at the head of csrc/det_corner_loss.hip).  Operands as v2x_det_loss_forward, plus anchors: DEVICE fp32
+ * [anchors_per_map][6] (x, y, w, h, sin, cos), 8-byte aligned; anchor i decodes through row i mod anchors_per_map, and n_anchors must be a multiple of
+ * anchors_per_map (V2X_EINVAL + v2x_last_error otherwise).  loc = sum over masked anchors of sum_k |corner_k(decode(loc_i)) - corner_k(decode(targets_i))|_2
+ * with the 'faf' decode (w = wa exp(clip(dw, -4, 4)), yaw = atan2(sa, ca) + atan2(ds, dc), 0 at ds = dc = 0) and box_corners' corner order; wh_swap != 0:
+ * h runs along the heading (Config.box_wh_axis = "h_along_heading").  The codes of an unmasked anchor are not read (inf / NaN there change nothing; its
+ * dloc row is 0); |D| = 0, ds = dc = 0 and a clipped dw / dh give gradient 0.  cls, out4 = {cls / n + loc / n, cls / n, loc / n, n = max(sum l_1, 1)},
+ * the workspace (v2x_det_loss_workspace_size(n_anchors) bytes), the launches (two forward, one backward; fixed order, bit-reproducible, capturable) and the
+ * incoming gradients (DEVICE scalars, NULL = 0) are v2x_det_loss_forward / _backward's. */
+int v2x_det_corner_loss_forward(const float *cls, const float *labels, const float *loc, const float *targets, const uint8_t *mask, const float *anchors,
+                                long long n_anchors, long long anchors_per_map, int wh_swap, float alpha, float *out4, float *workspace,
+                                v2x_stream_t stream);
+int v2x_det_corner_loss_backward(const float *cls, const float *labels, const float *loc, const float *targets, const uint8_t *mask, const float *anchors,
+                                 long long n_anchors, long long anchors_per_map, int wh_swap, float alpha, const float *out4, const float *g_loss,
+                                 const float *g_cls, const float *g_loc, float *dcls, float *dloc, v2x_stream_t stream);
 
 /* Rows a8 / f-3, the segmentation loss of a training step, forward and backward (replaces the nn.CrossEntropyLoss of
  * coperception/utils/SegModule.py::SegModule.step and its autograd backward -- not in /root/reference, README.md:101 names the scripts that call it;

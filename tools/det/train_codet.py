@@ -42,6 +42,9 @@ def build_parser():
     ap.add_argument("--targets", default="radius", choices=["radius", "iou"],
                     help="anchor assignment (DESIGN.md section 3.7): radius = the 0.75 m centre rule, built on the host per item; iou = rotated IoU with "
                          "thresholds and forced best match, one call on the GPU for all items of the step (v2x_det_assign_targets)")
+    ap.add_argument("--loss_type", default="faf_loss", choices=["faf_loss", "corner_loss"],
+                    help="localisation term (upstream's config.loss_type; DESIGN.md section 3.10): faf_loss = smooth-L1 on the six box codes; corner_loss = the "
+                         "distance between the four corners of the decoded prediction and of the decoded target")
     from v2x_sim_amd.utils import comm
     comm.add_arguments(ap)
     ap.add_argument("--engine", default="", choices=["", "torch", "hip", "hip-graph"],
@@ -63,7 +66,7 @@ def main(argv=None):
     from v2x_sim_amd.utils import comm
     if not torch.cuda.is_available():
         raise SystemExit("train_codet.py needs the MI355X")
-    config = Config("train", binary=True, only_det=True)
+    config = Config("train", binary=True, only_det=True, loss_type=args.loss_type)
     A = args.num_agent
     comm.refuse_channel_in_training(args)
     ckw = comm.model_kwargs(args, intermediate=args.com not in ("lowerbound", "upperbound"))

@@ -12,51 +12,8 @@
 // stays capturable).  The gradient formulas are the derivatives autograd forms for the expressions above, for ANY label pair (l_0, l_1):
 //     d cls / d c_j = -alpha_t [ -2 (1 - p_t) p_j (l_j - p_t) s + (1 - p_t)^2 (l_j - p_j (l_0 + l_1)) ],   s = sum_k l_k log p_k
 //     d loc / d x   = mask * (|d| < beta ? d / beta : sign(d)),   d = x - t
-#include "common.h"
-
-constexpr int DL_THREADS = 256;
-constexpr int DL_MAX_BLOCKS = 1024;
-
-struct DetLossArgs {
-    const float *cls, *lab, *loc, *tgt;   // [n][2], [n][2], [n][6], [n][6]
-    const uint8_t *mask;                  // [n] (bool)
-    long long n;                          // anchors
-    float alpha, beta;
-    float *part;                          // [n_blocks][3]: sum l_1, cls sum, loc sum
-    float *out;                           // [4]: loss, cls_loss, loc_loss, n (clamped)
-    const float *g_loss, *g_cls, *g_loc;  // incoming gradients (device scalars; null = 0)
-    float *dcls, *dloc;
-    int n_blocks;
-};
-
-struct FocalTerms {
-    float p0, p1, pt, s, alpha_t;
-};
-
-__device__ __forceinline__ FocalTerms focal_terms(float c0, float c1, float l0, float l1, float alpha) {
-    FocalTerms f;
-    const float m = fmaxf(c0, c1);
-    const float e0 = __expf(c0 - m), e1 = __expf(c1 - m);
-    const float lse = m + __logf(e0 + e1);
-    const float lp0 = c0 - lse, lp1 = c1 - lse;
-    const float inv = 1.0f / (e0 + e1);
-    f.p0 = e0 * inv;
-    f.p1 = e1 * inv;
-    f.pt = f.p0 * l0 + f.p1 * l1;
-    f.s = lp0 * l0 + lp1 * l1;
-    f.alpha_t = l1 * alpha + l0 * (1.0f - alpha);
-    return f;
-}
-
-// fixed-order sum of one value per thread over the workgroup (wave butterfly, then the four waves in wave order)
-__device__ __forceinline__ float block_sum(float v, float *red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
+// The corner form of the localisation term (loss_type = "corner_loss") lives in det_corner_loss.hip; det_loss_common.h holds what the two files share.
+#include "det_loss_common.h"
 
 __global__ __launch_bounds__(DL_THREADS) void det_loss_partial_kernel(const DetLossArgs a) {
     __shared__ float red[4];
@@ -88,32 +45,6 @@ __global__ __launch_bounds__(DL_THREADS) void det_loss_partial_kernel(const DetL
         a.part[blockIdx.x * 3 + 0] = s0;
         a.part[blockIdx.x * 3 + 1] = s1;
         a.part[blockIdx.x * 3 + 2] = s2;
-    }
-}
-
-// one workgroup: thread t adds partials t, t + 256, ... in fp64, then a fixed tree
-__global__ __launch_bounds__(DL_THREADS) void det_loss_finish_kernel(const DetLossArgs a) {
-    __shared__ double r[3][DL_THREADS];
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < a.n_blocks; b += DL_THREADS)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s[k] += (double)a.part[b * 3 + k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r[k][threadIdx.x] = s[k];
-    __syncthreads();
-    for (int w = DL_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) r[k][threadIdx.x] += r[k][threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const float n = fmaxf((float)r[0][0], 1.0f);
-        const float cl = (float)r[1][0] / n, ll = (float)r[2][0] / n;
-        a.out[0] = cl + ll;
-        a.out[1] = cl;
-        a.out[2] = ll;
-        a.out[3] = n;
     }
 }
 
@@ -151,12 +82,6 @@ __global__ __launch_bounds__(DL_THREADS) void det_loss_backward_kernel(const Det
             for (int k = 0; k < 3; ++k) dx[k] = make_float2(0.f, 0.f);
         }
     }
-}
-
-static int dl_blocks(long long n) {
-    long long b = (n + DL_THREADS * 8 - 1) / (DL_THREADS * 8);      // >= 8 anchors per thread
-    if (b < 1) b = 1;
-    return (int)(b < DL_MAX_BLOCKS ? b : DL_MAX_BLOCKS);
 }
 
 extern "C" long long v2x_det_loss_workspace_size(long long n_anchors) {

@@ -89,6 +89,8 @@ SIGNATURES = {
     "v2x_det_loss_workspace_size": (C.c_longlong, [C.c_longlong]),
     "v2x_det_loss_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_longlong, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "v2x_det_loss_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_longlong, C.c_float, C.c_float] + [C.c_void_p] * 7),
+    "v2x_det_corner_loss_forward": (C.c_int, [C.c_void_p] * 6 + [C.c_longlong, C.c_longlong, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v2x_det_corner_loss_backward": (C.c_int, [C.c_void_p] * 6 + [C.c_longlong, C.c_longlong, C.c_int, C.c_float] + [C.c_void_p] * 7),
     "v2x_seg_loss_workspace_size": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     "v2x_seg_loss_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "v2x_seg_loss_backward": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong, C.c_int] + [C.c_void_p] * 4),

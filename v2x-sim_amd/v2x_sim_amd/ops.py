@@ -709,7 +709,7 @@ from .ops_post import assign_targets, assign_targets_sparse_keys, conv2d_det, de
 from .ops_seg import median_frequency_weights, pad_box_lists, rasterize_seg, seg_grid  # noqa: E402,F401
 from .ops_track import assign_iou, hota_sequences, mot_sequences, sort_step  # noqa: E402,F401
 from .ops_train import (bn_train_backward, bn_train_forward, cast_pad_chsum, channel_sum, conv3x3_wgrad, det_loss_backward, det_loss_forward,  # noqa: E402,F401
-                        gru_gates, gru_gates_backward, gru_gates_nhwc, gru_gates_nhwc_backward, gru_gates_nhwc_ok, upcat, upcat_backward, v2v_message,
+                        det_corner_loss_backward, det_corner_loss_forward, gru_gates, gru_gates_backward, gru_gates_nhwc, gru_gates_nhwc_backward, gru_gates_nhwc_ok, upcat, upcat_backward, v2v_message,
                         seg_loss_backward, seg_loss_backward_packed, seg_loss_forward, seg_loss_shape_ok, v2v_message_backward, warp_affine, zero_insert)
 
 

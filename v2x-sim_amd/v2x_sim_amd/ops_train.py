@@ -143,6 +143,51 @@ def det_loss_backward(cls, labels, loc, targets, mask, alpha, beta, out4, g_loss
     return dcls, dloc
 
 
+def _corner_anchors(anchors, n, device):
+    """The anchor table as the corner-loss kernels take it: fp32 contiguous (M, 6) on the operands' device, M dividing n."""
+    _dev(anchors, torch.float32, "anchors")
+    if anchors.dim() != 2 or anchors.shape[1] != 6:
+        raise ValueError("det_corner_loss: anchors must be (M, 6) [x, y, w, h, sin, cos], got %s" % (tuple(anchors.shape),))
+    if anchors.device != device:
+        raise ValueError("det_corner_loss: anchors are on %s, the operands on %s" % (anchors.device, device))
+    M = anchors.shape[0]
+    if M == 0 or n % M:
+        raise ValueError("det_corner_loss: %d anchors are not a multiple of the %d anchors per map" % (n, M))
+    return M
+
+
+def det_corner_loss_forward(cls, labels, loc, targets, mask, anchors, wh_swap, alpha):
+    """v2x_det_corner_loss_forward: fp32 contiguous device tensors cls / labels (n, 2), loc / targets (n, 6), mask (n,) bool or uint8, anchors (M, 6) with
+    M dividing n (anchor i decodes through row i mod M); wh_swap: h runs along the heading ->
+    out4 (4,) fp32 = (loss, cls_loss, loc_loss, n_pos clamped to >= 1), loc_loss the corner distance."""
+    lib = _lib.load()
+    n = cls.numel() // 2
+    M = _corner_anchors(anchors, n, cls.device)
+    ws = torch.empty((lib.v2x_det_loss_workspace_size(n) // 4,), dtype=torch.float32, device=cls.device)
+    out = torch.empty((4,), dtype=torch.float32, device=cls.device)
+    m8 = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    _lib.check(lib.v2x_det_corner_loss_forward(_dev(cls, torch.float32, "cls"), _dev(labels, torch.float32, "labels"), _dev(loc, torch.float32, "loc"),
+                                               _dev(targets, torch.float32, "targets"), _dev(m8, torch.uint8, "mask"), _dev(anchors, torch.float32, "anchors"),
+                                               n, M, int(bool(wh_swap)), alpha, _dev(out, torch.float32, "out4"), _dev(ws, torch.float32, "workspace"),
+                                               _stream()), "v2x_det_corner_loss_forward")
+    return out
+
+
+def det_corner_loss_backward(cls, labels, loc, targets, mask, anchors, wh_swap, alpha, out4, g_loss, g_cls, g_loc):
+    """v2x_det_corner_loss_backward: -> (dcls like cls, dloc like loc) for the incoming gradients of (loss, cls_loss, loc_loss) (fp32 device scalars or None)."""
+    lib = _lib.load()
+    n = cls.numel() // 2
+    M = _corner_anchors(anchors, n, cls.device)
+    dcls, dloc = torch.empty_like(cls), torch.empty_like(loc)
+    m8 = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    gs = [None if g is None else _dev(g, torch.float32, "grad") for g in (g_loss, g_cls, g_loc)]
+    _lib.check(lib.v2x_det_corner_loss_backward(_dev(cls, torch.float32, "cls"), _dev(labels, torch.float32, "labels"), _dev(loc, torch.float32, "loc"),
+                                                _dev(targets, torch.float32, "targets"), _dev(m8, torch.uint8, "mask"), _dev(anchors, torch.float32, "anchors"),
+                                                n, M, int(bool(wh_swap)), alpha, _dev(out4, torch.float32, "out4"), gs[0], gs[1], gs[2],
+                                                _dev(dcls, torch.float32, "dcls"), _dev(dloc, torch.float32, "dloc"), _stream()), "v2x_det_corner_loss_backward")
+    return dcls, dloc
+
+
 def _seg_loss_operands(logits, labels, weight, c_pad=0):
     """-> (M, C) when the segmentation-loss kernels take these operands (fp32 contiguous device logits (..., C), C % 4 == 0, 4 <= C <= 32; uint8 labels, one per
     pixel; fp32 weight (C,) or None; c_pad by v2x_cast_pad_chsum_f32's rules), else None."""

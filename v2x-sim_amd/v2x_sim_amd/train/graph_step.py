@@ -42,7 +42,7 @@ def cached_step(optimizer, key, build=None):
 class GraphedTrainStep:
     _keys = _KEYS          # the batch entries copied into static tensors (GraphedSegTrainStep: its own)
 
-    def __init__(self, model, optimizer, data, batch_size, warmup=3, normalizer="positives"):
+    def __init__(self, model, optimizer, data, batch_size, warmup=3, normalizer="positives", loss_type="faf_loss", anchors=None, wh_axis="w_along_heading"):
         """model on the MI355X in train mode; optimizer: torch.optim.Adam(..., capturable=True) (lr may be a device tensor, see set_lr) or one without host-side state (plain SGD);
         data: one batch in FaFModule.step's format -- its shapes are the shapes of every later batch."""
         from .graph import train_forward
@@ -55,6 +55,13 @@ class GraphedTrainStep:
         use_hip_adam(optimizer)          # (a plain torch.optim.Adam steps on the library's kernel: train/optim.py)
         self.model, self.optimizer, self.batch_size = model, optimizer, batch_size
         self.normalizer = normalizer     # configs.Config.loss_normalizer (oracle/ASSUMPTIONS.md row 49)
+        # configs.Config.loss_type with what "corner_loss" decodes through (train/loss.py::detection_loss): the anchor table is put on the device HERE, so
+        # that the captured step reads a tensor that lives as long as the graph and copies nothing from the host
+        self.loss_type, self.wh_axis = loss_type, wh_axis
+        if loss_type == "corner_loss" and anchors is not None:
+            from .loss import corner_anchor_table
+            anchors = corner_anchor_table(anchors, data["bev_seq"].device)
+        self.anchors = anchors
         self.static = {k: data[k].clone() for k in self._keys if data.get(k) is not None}
         self.num_agent = None if data.get("num_agent") is None else data["num_agent"].clone().cpu()
         self._forward = train_forward
@@ -97,7 +104,8 @@ class GraphedTrainStep:
     def _step_body(self):
         s = self.static
         res = self._forward(self.model, s["bev_seq"], s.get("trans_matrices"), self.num_agent, self.batch_size)
-        loss, cls_loss, loc_loss = detection_loss(res, s["labels"], s["reg_targets"], s["reg_loss_mask"], normalizer=self.normalizer)
+        loss, cls_loss, loc_loss = detection_loss(res, s["labels"], s["reg_targets"], s["reg_loss_mask"], normalizer=self.normalizer,
+                                                  loss_type=self.loss_type, anchors=self.anchors, wh_axis=self.wh_axis)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.optimizer.step()

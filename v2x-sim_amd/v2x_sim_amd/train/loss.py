@@ -57,13 +57,111 @@ def _hip_loss_ok(cls, loc, labels, reg_targets, reg_loss_mask):
             and loc.shape[-1] == 6)
 
 
-def detection_loss(result, labels, reg_targets, reg_loss_mask, normalizer="positives"):
+LOSS_TYPES = ("faf_loss", "corner_loss")
+WH_AXES = ("w_along_heading", "h_along_heading")
+
+
+class _DetCornerLossHip(torch.autograd.Function):
+    """The loss with the corner localisation term on the hand-written kernels (csrc/det_corner_loss.hip): the launches, the outputs and the handling of
+    the incoming gradients are _DetLossHip's; anchors (M, 6) fp32 on the device, wh_swap a python bool."""
+
+    @staticmethod
+    def forward(ctx, cls, loc, lab, tgt, mask, anchors, wh_swap):
+        from .. import ops
+        ctx.set_materialize_grads(False)
+        out = ops.det_corner_loss_forward(cls, lab, loc, tgt, mask, anchors, wh_swap, ALPHA)
+        ctx.save_for_backward(cls, loc, lab, tgt, mask, anchors, out)
+        ctx.wh_swap = wh_swap
+        n_pos = out[3]
+        ctx.mark_non_differentiable(n_pos)
+        return out[0], out[1], out[2], n_pos
+
+    @staticmethod
+    def backward(ctx, g_loss, g_cls, g_loc, _g_npos=None):
+        from .. import ops
+        cls, loc, lab, tgt, mask, anchors, out = ctx.saved_tensors
+        gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_loss, g_cls, g_loc)]
+        dcls, dloc = ops.det_corner_loss_backward(cls, lab, loc, tgt, mask, anchors, ctx.wh_swap, ALPHA, out, *gs)
+        return dcls, dloc, None, None, None, None, None
+
+
+def corner_anchor_table(anchors, device, dtype=torch.float32):
+    """The anchors of one map as the corner loss reads them: (X, Y, A, 6) or (M, 6), tensor or numpy -> (M, 6) contiguous on `device`."""
+    a = anchors if isinstance(anchors, torch.Tensor) else torch.as_tensor(anchors)
+    if a.dim() < 2 or a.shape[-1] != 6:
+        raise ValueError("anchors must be (X, Y, A, 6) or (M, 6) [x, y, w, h, sin, cos], got %s" % (tuple(a.shape),))
+    return a.reshape(-1, 6).to(device=device, dtype=dtype).contiguous()
+
+
+def decode_corners(codes, anchors, wh_axis="w_along_heading"):
+    """codes (..., M, 6), anchors (M, 6) -> (..., M, 4, 2): the 'faf' decode of utils/postprocess.py::decode_boxes followed by box_corners' four corners
+    (same order, same reading of wh_axis), in differentiable PyTorch ops.  atan2(ds, dc) at ds = dc = 0 has value 0 and gradient 0 (torch's own backward
+    divides 0 by 0 there): such a pair is replaced by the constants (0, 1) before the call."""
+    ds, dc = codes[..., 4], codes[..., 5]
+    z = (ds == 0) & (dc == 0)
+    dyaw = torch.atan2(torch.where(z, torch.zeros_like(ds), ds), torch.where(z, torch.ones_like(dc), dc))
+    x = anchors[:, 0] + codes[..., 0]
+    y = anchors[:, 1] + codes[..., 1]
+    w = anchors[:, 2] * torch.exp(torch.clamp(codes[..., 2], -4.0, 4.0))
+    h = anchors[:, 3] * torch.exp(torch.clamp(codes[..., 3], -4.0, 4.0))
+    yaw = torch.atan2(anchors[:, 4], anchors[:, 5]) + dyaw
+    if wh_axis == "h_along_heading":
+        w, h = h, w
+    c, s = torch.cos(yaw)[..., None], torch.sin(yaw)[..., None]
+    ox = w[..., None] * torch.tensor([0.5, -0.5, -0.5, 0.5], dtype=codes.dtype, device=codes.device)
+    oy = h[..., None] * torch.tensor([0.5, 0.5, -0.5, -0.5], dtype=codes.dtype, device=codes.device)
+    return torch.stack([x[..., None] + ox * c - oy * s, y[..., None] + ox * s + oy * c], -1)
+
+
+def corner_distance_sum(loc, reg_targets, reg_loss_mask, anchors, wh_axis="w_along_heading"):
+    """The corner localisation term before its normaliser: loc, reg_targets (N, M, 6), reg_loss_mask (N, M, 1) bool, anchors (M, 6)
+    -> sum over the selected anchors of the four distances between the corners of the decoded prediction and of the decoded target.
+    The codes of an unselected anchor are replaced by zeros BEFORE the decode (torch.where, not a masked sum: inf or NaN there would give inf * 0): such an
+    anchor decodes to the same box twice, contributes exactly 0 and receives exactly zero gradient.  |D| at D = 0 has gradient 0 (torch's sqrt has none):
+    a zero squared length is replaced by the constant 1 under the root.  No data-dependent shape, no host synchronisation: capturable."""
+    x = torch.where(reg_loss_mask, loc, torch.zeros_like(loc))
+    t = torch.where(reg_loss_mask, reg_targets, torch.zeros_like(reg_targets))
+    d = decode_corners(x, anchors, wh_axis) - decode_corners(t, anchors, wh_axis)
+    q = (d * d).sum(-1)
+    zero = q == 0
+    return torch.where(zero, torch.zeros_like(q), torch.sqrt(torch.where(zero, torch.ones_like(q), q))).sum()
+
+
+def detection_loss(result, labels, reg_targets, reg_loss_mask, normalizer="positives", loss_type="faf_loss", anchors=None, wh_axis="w_along_heading"):
     """result: {'cls' (N, X*Y*A, 2), 'loc' (N, X, Y, A, 1, 6)};  labels (N, X, Y, A, 2);  reg_targets (N, X, Y, A, 1, 6);
     reg_loss_mask (N, X, Y, A, 1) bool  ->  (loss, cls_loss, loc_loss) scalars.  On the MI355X with the HIP training engine (TRAIN_HIP, and
-    TRAIN_LOSS_HIP != 0) and fp32 operands: three launches of csrc/det_loss.hip; otherwise the PyTorch ops below (the specification)."""
+    TRAIN_LOSS_HIP != 0) and fp32 operands: three launches of csrc/det_loss.hip; otherwise the PyTorch ops below (the specification).
+    loss_type (configs.Config.loss_type, upstream's switch): "faf_loss" = the smooth-L1 term above; "corner_loss" = the distance between the four
+    corners of the decoded prediction and of the decoded target (corner_distance_sum), same classification term, same
+    normaliser.  It needs `anchors` -- (X, Y, A, 6) or (M, 6), tensor or numpy, the anchors of ONE map -- and reads `wh_axis` (Config.box_wh_axis);
+    under the same switches it runs as three launches of csrc/det_corner_loss.hip."""
     if normalizer not in ("positives", "batch"):
         raise ValueError("normalizer must be 'positives' or 'batch'")
+    if loss_type not in LOSS_TYPES:
+        raise ValueError("loss_type must be one of %s, got %r" % (LOSS_TYPES, loss_type))
     n = result["cls"].shape[0]
+    if loss_type == "corner_loss":
+        if anchors is None:
+            raise ValueError("loss_type='corner_loss' decodes the boxes: it needs the anchors of one map")
+        if wh_axis not in WH_AXES:
+            raise ValueError("wh_axis must be one of %s" % (WH_AXES,))
+        loc = result["loc"]
+        table = corner_anchor_table(anchors, loc.device, loc.dtype)
+        if loc.numel() != n * table.shape[0] * 6:
+            raise ValueError("corner_loss: loc %s does not hold %d maps of %d anchors" % (tuple(loc.shape), n, table.shape[0]))
+        if _hip_loss_ok(result["cls"], loc, labels, reg_targets, reg_loss_mask):
+            loss, cls_loss, loc_loss, n_pos = _DetCornerLossHip.apply(result["cls"].contiguous(), loc.contiguous(), labels.contiguous(), reg_targets.contiguous(),
+                                                                      reg_loss_mask.contiguous(), table, wh_axis == "h_along_heading")
+            if normalizer == "batch":
+                k = n_pos / float(n)
+                return loss * k, cls_loss * k, loc_loss * k
+            return loss, cls_loss, loc_loss
+        lab = labels.reshape(n, -1, 2).to(result["cls"].dtype)
+        n_pos = lab[..., 1].sum().clamp(min=1.0) if normalizer == "positives" else torch.tensor(float(n), dtype=result["cls"].dtype, device=result["cls"].device)
+        cls_loss = focal_loss(result["cls"], lab).sum() / n_pos
+        loc_loss = corner_distance_sum(loc.reshape(n, -1, 6), reg_targets.reshape(n, -1, 6).to(loc.dtype), reg_loss_mask.reshape(n, -1, 1).to(torch.bool),
+                                       table, wh_axis) / n_pos
+        return cls_loss + loc_loss, cls_loss, loc_loss
     if _hip_loss_ok(result["cls"], result["loc"], labels, reg_targets, reg_loss_mask):
         loss, cls_loss, loc_loss, n_pos = _DetLossHip.apply(result["cls"].contiguous(), result["loc"].contiguous(), labels.contiguous(),
                                                             reg_targets.contiguous(), reg_loss_mask.contiguous())

@@ -27,7 +27,7 @@ Host-side switches (this module):
                    instead of once per ego; bit-identical); 0: the plain grid
     SEG_FUSE    1  segmentation models: conv8_2 and the 1x1 class head as one halo launch (the 32-channel map never reaches HBM; bit-identical); 0: two layers
     TRAIN_GATES_HIP 1  with TRAIN_HIP: the ConvGRU's gate arithmetic of the fusion stage as one launch forward and one backward (csrc/gru_train.hip)
-    TRAIN_LOSS_HIP 1  with TRAIN_HIP: the detection loss and its gradients as three launches of csrc/det_loss.hip (0: ~45 PyTorch-ROCm ops)
+    TRAIN_LOSS_HIP 1  with TRAIN_HIP: the detection loss and its gradients as three launches of csrc/det_loss.hip (Config.loss_type = "corner_loss": of csrc/det_corner_loss.hip); 0: PyTorch-ROCm ops, ~45 for smooth-L1
     TRAIN_PACK_BATCH 1  with TRAIN_HIP: the packed weights of all layers rebuilt by ONE launch after an optimizer step (0: one launch per layer)
     PARITY_CLASS 3  pack the decoder `_1` layers the parity-class kernels cover with pre-summed 2x2-tap weights for the x2-upsampled source (-37 % MACs;
                    the sums are formed in fp32 and rounded to bf16 once): 2 = conv8_1 (w_layout 3, resident weights) and conv5_1 / conv6_1 (w_layout 4,

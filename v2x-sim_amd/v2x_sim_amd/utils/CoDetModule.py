@@ -44,6 +44,15 @@ class FaFModule(object):
         self.loss_normalizer = getattr(config, "loss_normalizer", "positives")
         if self.wh_axis not in postprocess.WH_AXES:
             raise ValueError("config.box_wh_axis must be one of %s" % (postprocess.WH_AXES,))
+        # upstream's loss_calculator switch (train/loss.py::detection_loss): "faf_loss" = smooth-L1 on the codes, "corner_loss" = the corner distance
+        self.loss_type = getattr(config, "loss_type", "faf_loss")
+        from ..train.loss import LOSS_TYPES
+        if self.loss_type not in LOSS_TYPES:
+            raise ValueError("config.loss_type must be one of %s, got %r" % (LOSS_TYPES, self.loss_type))
+        if self.loss_type == "corner_loss" and not (getattr(config, "only_det", True) and getattr(config, "code_type", "faf") == "faf"
+                                                    and getattr(config, "pred_len", 1) == 1):
+            raise NotImplementedError("loss_type='corner_loss' covers only_det=True, code_type='faf', pred_len=1 (DESIGN.md section 3.10)")
+        self._loss_anchors = None         # the anchors of one map on the device, (M, 6): what the corner loss decodes through
         self._graphed = None              # (batch-shape key, GraphedTrainStep) when V2X_TRAIN_GRAPH=1
 
     def step(self, data, batch_size, num_agent=5):
@@ -62,20 +71,32 @@ class FaFModule(object):
             # V2X_TRAIN_HIP=1 V2X_TRAIN_GRAPH=1: the whole step as one hipGraph (train/graph_step.py), rebuilt when the batch shape changes
             from ..train.graph_step import GraphedTrainStep, cached_step
             key = self._graph_key(data, batch_size)
-            step = cached_step(self.optimizer, key, lambda: GraphedTrainStep(self.model, self.optimizer, data, batch_size, normalizer=self.loss_normalizer))
+            step = cached_step(self.optimizer, key, lambda: GraphedTrainStep(self.model, self.optimizer, data, batch_size, normalizer=self.loss_normalizer,
+                                                                             **self._loss_kwargs(bev.device)))
             self._graphed = (key, step)
             loss, cls_loss, loc_loss = step(data)
             return loss.item(), cls_loss.item(), loc_loss.item()
         result = train_forward(self.model, bev, data.get("trans_matrices"), data.get("num_agent"), batch_size)
-        loss, cls_loss, loc_loss = detection_loss(result, data["labels"], data["reg_targets"], data["reg_loss_mask"], normalizer=self.loss_normalizer)
+        loss, cls_loss, loc_loss = detection_loss(result, data["labels"], data["reg_targets"], data["reg_loss_mask"], normalizer=self.loss_normalizer,
+                                                  **self._loss_kwargs(bev.device))
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.optimizer.step()
         packing.stepped(self.optimizer)       # (an optimizer without step hooks: stamp the parameters here)
         return loss.item(), cls_loss.item(), loc_loss.item()
 
+    def _loss_kwargs(self, device):
+        """detection_loss's loss_type / anchors / wh_axis; the anchor table goes to the device once (as _anchors_dev does for post-processing)."""
+        if self.loss_type != "corner_loss":
+            return {"loss_type": self.loss_type}
+        if self._loss_anchors is None or self._loss_anchors.device != device:
+            from ..train.loss import corner_anchor_table
+            self._loss_anchors = corner_anchor_table(self.anchors, device)
+        return {"loss_type": self.loss_type, "anchors": self._loss_anchors, "wh_axis": self.wh_axis}
+
     def _graph_key(self, data, batch_size):
-        return (id(self.model),) + tuple(tuple(data[k].shape) for k in ("bev_seq", "labels", "reg_targets", "reg_loss_mask")) + (batch_size, self.loss_normalizer)
+        return (id(self.model),) + tuple(tuple(data[k].shape) for k in ("bev_seq", "labels", "reg_targets", "reg_loss_mask")) + (batch_size, self.loss_normalizer,
+                                                                                                                                self.loss_type)
 
     def _graph_ok(self, data, batch_size):
         from .. import tuning
