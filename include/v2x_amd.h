@@ -699,6 +699,34 @@ int v2x_rotated_iou(const float *boxes_a, int na, const float *boxes_b, int nb, 
 int v2x_match_detections(const float *det_boxes, const int32_t *det_count, int det_cap, const float *gt_boxes,
                          const int32_t *gt_count, int gt_cap, int n_img, float iou_thr, int32_t *tp, float *best_iou,
                          v2x_stream_t stream);
+/* v2x_det_map: the AP table of a whole split -- all maps, all agents (groups), all IoU thresholds -- in ONE call: four launches, no atomics, no
+ * allocation, no host synchronisation (capturable), bit-reproducible.  The frozen rule is DESIGN.md section 3.11.
+ * INPUT (device): det_boxes fp32 [n_img][det_cap][5] (x, y, w, h, yaw), each map in DESCENDING score order (what v2x_det_postprocess emits);
+ *   det_scores fp32 [n_img][det_cap], FINITE (a NaN or infinite score of a counted detection is out of contract); det_count int32 [n_img];
+ *   gt_boxes fp32 [n_img][gt_cap][5]; gt_count int32 [n_img]; counts are clamped to [0, cap] as v2x_match_detections does.  group int32 [n_img]:
+ *   the agent of each map in [0, n_groups); any other value (-1 by convention: an agent with an empty sweep) keeps the map out of every count and
+ *   list -- its scores are never read.  iou_thr fp32 [n_thr] on the DEVICE, each in (0, 1], any order, duplicates allowed.
+ * MATCHING: v2x_match_detections' rule and arithmetic (one definition, csrc/det_match.h).  A detection's ground truth is the one of highest rotated
+ *   IoU (fp64 clip), lowest index on ties, none at IoU 0 -- found ONCE and shared by all thresholds; the greedy walk in score order keeps one
+ *   "taken" set PER THRESHOLD (true positive at t iff IoU >= (double)iou_thr[t] and the ground truth is free at t).
+ * RANKING: per group, stable descending by the fp32 score VALUE (-0.0 and +0.0 tie); ties by ascending map index, then ascending position in the
+ *   map -- numpy's stable argsort(-scores) over the image-major concatenation.
+ * AP: mmdet "area" mode in float64 (v2x_sim_amd/utils/postprocess.py::average_precision): along the ranked list tp_i, fp_i cumulative counts,
+ *   recall_i = tp_i / num_gt, precision_i = tp_i / (tp_i + fp_i), envelope = suffix maximum of the precision, area = sum over the positions where
+ *   the recall changes of (recall step) x envelope.  num_gt == 0 or no detections: 0.
+ * OUTPUT (device; EVERY element is written, the caller clears nothing): ap double [n_groups][n_thr]; num_gt, num_det long long [n_groups];
+ *   num_tp long long [n_groups][n_thr]; tp uint8 [n_thr][n_img][det_cap] or NULL (1 / 0; entries >= det_count: 0; a map outside every group is
+ *   matched like any other); rank int32 [n_img][det_cap] or NULL (the detection's position in its group's ranked list; -1 beyond the count and
+ *   for a map outside every group).
+ * Limits: det_cap in [1, 4096], gt_cap in [1, 8192], n_groups in [1, 64], n_thr in [1, 8], n_img * det_cap < 2^31.  workspace: DEVICE,
+ *   workspace_bytes >= v2x_det_map_workspace_size (-1 for sizes out of range); it needs no initialisation.  Bad sizes, a NULL required pointer or a
+ *   short workspace: V2X_EINVAL with a v2x_last_error() text, nothing launched.  n_img == 0: nothing to do (V2X_OK), whatever the other arguments
+ *   are -- nothing is written. */
+long long v2x_det_map_workspace_size(long long n_img, int det_cap, int gt_cap, int n_groups, int n_thr);
+int v2x_det_map(const float *det_boxes, const float *det_scores, const int32_t *det_count, int det_cap, const float *gt_boxes,
+                const int32_t *gt_count, int gt_cap, const int32_t *group, long long n_img, int n_groups, const float *iou_thr, int n_thr,
+                double *ap, long long *num_gt, long long *num_det, long long *num_tp, uint8_t *tp, int32_t *rank, void *workspace,
+                long long workspace_bytes, v2x_stream_t stream);
 
 /* ---------------------------------------------------------------- f-5: tracking (tools/track: SORT on the detections)
  * v2x_assign_iou: the association step alone on caller-supplied IoU matrices.  iou fp32 [n][cap_r][cap_c] (rows = detections, columns = tracks),

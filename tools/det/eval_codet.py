@@ -17,7 +17,12 @@ came from neighbours is printed after the scores.
 --p_com_outage p (every directed link down with probability p at every step) and --pose_noise sigma (Gaussian noise, metres, on the translation of the
 agent-to-agent transforms) are drawn on the device from (--channel_seed, step).  They are an evaluation condition: no checkpoint
 records them; --com lowerbound / upperbound / late refuse them, when2com / who2com take --pose_noise only.  The realised share of links up is printed
-after the scores."""
+after the scores.
+
+    python tools/det/eval_codet.py --data /path/V2X-Sim-det/test --com v2v --resume ckpt.pth --map_engine device
+
+--map_engine host | device (default host) travels like every other flag: the driver is tools/det/map_codet.py, which IS test_codet.py for `host` and
+scores the same run with one v2x_det_map call for all agents and both thresholds for `device` (same lines, same returned dict)."""
 import os
 import sys
 
@@ -28,9 +33,9 @@ for _p in (ROOT, os.path.join(ROOT, "v2x-sim_amd"), os.path.dirname(os.path.absp
 
 
 def main(argv=None):
-    import test_codet
+    import map_codet
     from v2x_sim_amd.utils import comm
-    return comm.run_eval_driver(test_codet.main, sys.argv[1:] if argv is None else argv)
+    return comm.run_eval_driver(map_codet.main, sys.argv[1:] if argv is None else argv)
 
 
 if __name__ == "__main__":

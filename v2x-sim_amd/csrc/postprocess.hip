@@ -18,6 +18,7 @@
 //      threads in parallel (__syncthreads_or), so the serial depth is the number of candidates, not candidates x kept.
 #include "common.h"
 #include "det_geom.h"   // rotated-box IoU, stand-up box and the suppression test: shared with late_fuse.hip
+#include "det_match.h"  // the per-detection ground-truth choice of the matching: shared with det_map.hip
 
 __global__ __launch_bounds__(256) void rotated_iou_kernel(const float *__restrict__ a, int na, const float *__restrict__ b, int nb,
                                                           float *__restrict__ iou) {
@@ -49,31 +50,7 @@ __global__ __launch_bounds__(256) void match_detections_kernel(const float *__re
     for (int g = tid; g < ng; g += 256) taken[g] = 0;
     __syncthreads();
     for (int j = 0; j < nd; ++j) {
-        const float *d = det + ((size_t)img * det_cap + j) * 5;
-        double best = 0.0;
-        int arg = -1;
-        for (int g = tid; g < ng; g += 256) {
-            const double v = rotated_iou_d(d, gt + ((size_t)img * gt_cap + g) * 5);
-            if (v > best) {
-                best = v;
-                arg = g;
-            }
-        }
-        s_best[tid] = best;
-        s_arg[tid] = arg;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if (tid < st) {
-                const double o = s_best[tid + st];
-                const int oa = s_arg[tid + st];
-                // larger IoU wins; equal IoU: the lower ground-truth index (a sequential scan keeps the first maximum)
-                if (o > s_best[tid] || (o == s_best[tid] && oa >= 0 && (s_arg[tid] < 0 || oa < s_arg[tid]))) {
-                    s_best[tid] = o;
-                    s_arg[tid] = oa;
-                }
-            }
-            __syncthreads();
-        }
+        det_best_gt(det + ((size_t)img * det_cap + j) * 5, gt + (size_t)img * gt_cap * 5, ng, tid, s_best, s_arg);   // det_match.h
         if (tid == 0) {
             const int a0 = s_arg[0];
             const bool hit = a0 >= 0 && s_best[0] >= (double)thr && !taken[a0];

@@ -210,3 +210,52 @@ def match_detections(det_boxes, det_count, gt_boxes, gt_count, iou_thr, want_iou
                                         _dev(best, torch.float32, "best_iou") if best is not None else None, _stream()),
                "v2x_match_detections")
     return (tp, best) if want_iou else tp
+
+
+DET_MAP_MAX_THR, DET_MAP_MAX_GROUPS, DET_MAP_MAX_DET, DET_MAP_MAX_GT = 8, 64, 4096, 8192      # csrc/det_map.hip
+
+
+def det_map(det_boxes, det_scores, det_count, gt_boxes, gt_count, group, iou_thrs=(0.5, 0.7), n_groups=1, want_flags=False):
+    """The AP table of a whole split in ONE v2x_det_map call (csrc/det_map.hip).  det_boxes (n, det_cap, 5) fp32, each map
+    in descending score order, det_scores (n, det_cap) fp32 (finite), det_count (n,) int32, gt_boxes (n, gt_cap, 5) fp32, gt_count (n,) int32,
+    group (n,) int32 (the agent of each map in [0, n_groups); -1: the map takes no part), all on the device; iou_thrs: 1..8 floats in (0, 1] (or a
+    device fp32 tensor) -> ap (n_groups, T) float64, num_gt (n_groups,) int64, num_det (n_groups,) int64, num_tp (n_groups, T) int64
+    [, tp (T, n, det_cap) uint8, rank (n, det_cap) int32] on the device."""
+    lib = _lib.load()
+    n, det_cap = int(det_boxes.shape[0]), int(det_boxes.shape[1])
+    gt_cap = int(gt_boxes.shape[1])
+    dev = det_boxes.device
+    if torch.is_tensor(iou_thrs):
+        thr = iou_thrs.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        vals = thr.cpu().tolist()             # at most eight floats: the C entry cannot read device values, so the range is checked here
+    else:
+        vals = [float(v) for v in iou_thrs]
+        thr = None
+    if not all(0.0 < v <= 1.0 for v in vals):
+        raise ValueError("det_map: every IoU threshold must lie in (0, 1], got %s" % (vals,))
+    if thr is None:
+        thr = torch.tensor(vals, dtype=torch.float32, device=dev)
+    T, n_groups = int(thr.numel()), int(n_groups)
+    if not (1 <= T <= DET_MAP_MAX_THR and 1 <= n_groups <= DET_MAP_MAX_GROUPS):
+        raise ValueError("det_map: %d thresholds (1..%d), %d groups (1..%d)" % (T, DET_MAP_MAX_THR, n_groups, DET_MAP_MAX_GROUPS))
+    if det_scores.shape != (n, det_cap) or det_count.shape != (n,) or gt_count.shape != (n,) or group.shape != (n,) or gt_boxes.shape[0] != n:
+        raise ValueError("det_map: det_scores (n, det_cap), det_count, gt_count, group (n,) and gt_boxes (n, gt_cap, 5) must agree with det_boxes")
+    ap = torch.zeros((n_groups, T), dtype=torch.float64, device=dev)
+    num_gt = torch.zeros((n_groups,), dtype=torch.int64, device=dev)
+    num_det = torch.zeros((n_groups,), dtype=torch.int64, device=dev)
+    num_tp = torch.zeros((n_groups, T), dtype=torch.int64, device=dev)
+    tp = torch.zeros((T, n, det_cap), dtype=torch.uint8, device=dev) if want_flags else None
+    rank = torch.full((n, det_cap), -1, dtype=torch.int32, device=dev) if want_flags else None
+    if n:
+        nbytes = lib.v2x_det_map_workspace_size(n, det_cap, gt_cap, n_groups, T)
+        if nbytes < 0:
+            raise ValueError("det_map: sizes out of range (det_cap %d in [1, 4096], gt_cap %d in [1, 8192], n * det_cap < 2^31)" % (det_cap, gt_cap))
+        ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.v2x_det_map(_dev(det_boxes, torch.float32, "det_boxes"), _dev(det_scores, torch.float32, "det_scores"),
+                                   _dev(det_count, torch.int32, "det_count"), det_cap, _dev(gt_boxes, torch.float32, "gt_boxes"),
+                                   _dev(gt_count, torch.int32, "gt_count"), gt_cap, _dev(group, torch.int32, "group"), n, n_groups,
+                                   _dev(thr, torch.float32, "iou_thr"), T, _dev(ap, torch.float64, "ap"), _dev(num_gt, torch.int64, "num_gt"),
+                                   _dev(num_det, torch.int64, "num_det"), _dev(num_tp, torch.int64, "num_tp"),
+                                   _dev(tp, torch.uint8, "tp") if want_flags else None, _dev(rank, torch.int32, "rank") if want_flags else None,
+                                   _dev(ws, torch.uint8, "workspace"), int(nbytes), _stream()), "v2x_det_map")
+    return (ap, num_gt, num_det, num_tp, tp, rank) if want_flags else (ap, num_gt, num_det, num_tp)
