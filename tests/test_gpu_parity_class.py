@@ -282,7 +282,7 @@ def test_parity_class_kernels_random_shapes(device, C0, C1, Cout, N, H, W):
         pc = packing.pack_conv_halo_parity("sweep", conv.weight, scale, shift, C0=C0, C1=C1, device=device)
     else:
         pc = packing.pack_conv_stream_parity("sweep", conv.weight, scale, shift, C0=C0, C1=C1, device=device)
-    assert pc.w_layout in (3, 4) and ops.halo_eligible(H, W, pc.w_layout, max(C0, C1), Cout)
+    assert pc.w_layout in (3, 4) and ops.covers(pc, H, W)
     got = from_nhwc(_run(ops, pc, x_up, x_sk, device))
     ref = _same_operands_ref(packing, conv, bn, x_up, x_sk, C0)
     assert got.shape == ref.shape

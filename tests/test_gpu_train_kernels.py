@@ -241,6 +241,37 @@ def test_hip_graph_conv_extents_without_a_kernel_take_the_torch_path(device, H, 
     assert float((conv_d.weight.grad.cpu() - conv_r.weight.grad).abs().max()) <= 1e-2 * float(conv_r.weight.grad.abs().max())
 
 
+def test_hip_graph_upcat_conv_too_wide_for_the_halo_tables_takes_the_unfused_path(device):
+    """upcat_conv3x3 asks the library whether its three halo launches have a kernel (hip_graph.upcat_conv_covered).  A full-resolution map
+    of 8 x 1664 tiles by 8 x 32 but is too wide for the halo kernels' 20-bit DMA tables at 64 channels: the fused form was chosen and its launch
+    refused (V2XLibraryError); now the layer runs as conv3x3(upcat(...)) and matches fp32 autograd on the same bf16-rounded operands to
+    test_hip_graph_conv_function_vs_autograd's bars."""
+    from v2x_sim_amd.train import hip_graph
+    g = torch.Generator().manual_seed(1664)
+    lo = torch.randn(1, 4, 832, 64, generator=g).to(torch.bfloat16)
+    skip = torch.randn(1, 8, 1664, 32, generator=g).to(torch.bfloat16)
+    conv_r = torch.nn.Conv2d(96, 32, 3, 1, 1)
+    with torch.no_grad():
+        conv_r.weight.copy_((conv_r.weight * 2).to(torch.bfloat16).float())
+    conv_d = torch.nn.Conv2d(96, 32, 3, 1, 1).to(device)
+    conv_d.load_state_dict(conv_r.state_dict())
+    dy = torch.randn(1, 8, 1664, 32, generator=g).to(torch.bfloat16)
+    lo_r = lo.float().permute(0, 3, 1, 2).requires_grad_(True)
+    skip_r = skip.float().permute(0, 3, 1, 2).requires_grad_(True)
+    yr = conv_r(torch.cat((F.interpolate(lo_r, scale_factor=2, mode="nearest"), skip_r), 1))
+    yr.backward(dy.float().permute(0, 3, 1, 2))
+    assert not hip_graph.upcat_conv_covered(8, 1664) and hip_graph.hip_eligible(conv_d.weight, 1, 8, 1664)
+    lo_d, skip_d = lo.to(device).requires_grad_(True), skip.to(device).requires_grad_(True)
+    yd = hip_graph.upcat_conv3x3(lo_d, skip_d, conv_d)
+    yd.backward(dy.to(device))
+    rel = lambda got, ref: float((got.cpu().float() - ref).abs().max()) / float(ref.abs().max())   # noqa: E731
+    errs = (rel(yd.detach(), yr.detach().permute(0, 2, 3, 1)), rel(lo_d.grad, lo_r.grad.permute(0, 2, 3, 1)), rel(skip_d.grad, skip_r.grad.permute(0, 2, 3, 1)),
+            rel(conv_d.weight.grad, conv_r.weight.grad))
+    print("upcat_conv3x3 8 x 1664 unfused: y %.2e d_lo %.2e d_skip %.2e dw %.2e" % errs)
+    assert max(errs[:3]) <= 2.0 ** -7 and errs[3] <= 2e-5
+    assert torch.allclose(conv_d.bias.grad.cpu(), conv_r.bias.grad, rtol=1e-4, atol=1e-3)
+
+
 def test_hip_graph_training_step_vs_fp32_graph(device, monkeypatch, tune):
     """V2X_TRAIN_HIP=1: a FaFNet training step (batch-statistics BN) on the bf16 NHWC HIP graph against the fp32 MIOpen graph: the
     loss within 2 %, the running statistics of every BN within 2 % of their scale, and parameter gradients that point the same way:

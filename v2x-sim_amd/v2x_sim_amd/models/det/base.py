@@ -312,7 +312,7 @@ class DetModelBase(nn.Module):
         else:
             x = LidarDecoder.run(pk["dec"], *feats)
         det = getattr(pk["heads"], "det", None)
-        if (req is not None and det is not None and x.shape[1] % 8 == 0 and x.shape[2] % 32 == 0 and x.shape[1] * x.shape[2] * 6 < (1 << 20)
+        if (req is not None and det is not None and ops.covers(det, x.shape[1], x.shape[2])
                 and (self.anchor_num_per_loc, self.category_num, self.box_code_size, self.out_seq_len) == (6, 2, 6, 1)):
             return {"det": ops.conv2d_det(det, x, req[0], req[1])}
         return self.get_cls_loc_result(x, pk["heads"])

@@ -65,7 +65,7 @@ class SegHeadMixin(object):
         """Decoder + class head -> fp32 NHWC logits; conv8_2 and the head as one launch where the map tiles (tuning switch SEG_FUSE)."""
         fused = pk.get("seg_fused")
         x0 = feats[0]
-        if fused is not None and tuning.get("SEG_FUSE") != 0 and ops.halo_eligible(x0.shape[1], x0.shape[2], 1, 32):
+        if fused is not None and tuning.get("SEG_FUSE") != 0 and ops.covers(fused, x0.shape[1], x0.shape[2]):
             return ops.conv2d(fused, LidarDecoder.run(pk["dec"], *feats, last=False))
         return ops.conv2d(pk["seg"], LidarDecoder.run(pk["dec"], *feats))
 

@@ -5,6 +5,7 @@ happens inside libv2x_amd.so.  Every wrapper refuses non-device tensors -- there
 is deliberately no eager/CPU fallback.
 """
 import ctypes as C
+import functools
 
 import torch
 
@@ -52,8 +53,6 @@ class latency_dispatch:
 
 def latency_entry(fn):
     """Decorator of the plain single-GPU model entries (forward_nhwc of every model class): launches inside are declared latency launches."""
-    import functools
-
     @functools.wraps(fn)
     def wrapped(*a, **k):
         with latency_dispatch():
@@ -66,38 +65,75 @@ def latency_launches():
     return sb == 1 or (sb == 2 and getattr(_latency, "depth", 0) > 0)
 
 
-def _conv_desc(pc, N, H, W):
+def _conv_shape(pc, N, H, W):
     """What the packed layer and the extent determine of a v2x_conv_desc; the caller adds the tensors."""
     d = ConvDesc()
     d.C0, d.C1, d.up0 = pc.C0, pc.C1, pc.up0
     d.N, d.H, d.W = N, H, W
     d.ksize, d.stride, d.pad = pc.ksize, pc.stride, pc.pad
     d.Cout, d.w_rows, d.w_kpad = pc.Cout, pc.w_rows, pc.w_kpad
-    d.weight = pc.weight.data_ptr()
-    d.scale = pc.scale.data_ptr()
-    d.shift = pc.shift.data_ptr() if pc.shift is not None else None
     d.epilogue, d.relu = pc.epilogue, int(bool(pc.relu))
     d.w_layout = pc.w_layout or 0
     if pc.Cout2:
         d.Cout2, d.relu2 = pc.Cout2, int(bool(pc.relu2))
+    return d
+
+
+def _conv_desc(pc, N, H, W):
+    """_conv_shape with the layer's packed parameters; the caller adds the activations and the output."""
+    d = _conv_shape(pc, N, H, W)
+    d.weight = pc.weight.data_ptr()
+    d.scale = pc.scale.data_ptr()
+    d.shift = pc.shift.data_ptr() if pc.shift is not None else None
+    if pc.Cout2:
         d.weight2, d.scale2, d.shift2 = pc.weight2.data_ptr(), pc.scale2.data_ptr(), pc.shift2.data_ptr()
     return d
 
 
-_NEVER_READ = 16   # placeholder address of conv_kernel_name's activations and output: non-null and 16-byte aligned as the dispatch asks, never dereferenced
+_NEVER_READ = 16   # placeholder address of every tensor of a plan descriptor: non-null and 16-byte aligned as the dispatch asks, never dereferenced
+
+
+def _plan_desc(pc, N, H, W, bits):
+    """The descriptor conv_kernel_name and covers hand to v2x_conv2d_plan: _conv_shape with a placeholder for every tensor (so a PackedConv that
+    carries no tensors yet -- packing.train_conv_shape -- can be asked about), one unsplit output window, no split-K."""
+    d = _conv_shape(pc, N, H, W)
+    d.in0 = d.weight = d.scale = d.shift = d.out = _NEVER_READ
+    if pc.C1:
+        d.in1 = _NEVER_READ
+    if pc.Cout2:
+        d.weight2 = d.scale2 = d.shift2 = _NEVER_READ
+    if bits:
+        d.in_format, d.in_zbits = 1, 1
+    d.out_cstride = pc.Cout2 or pc.Cout
+    if pc.epilogue == _lib.V2X_EPI_DET:      # the candidate epilogue's outputs as conv2d_det sets them: keys, codes (6 per candidate), counts
+        d.out2, d.out2_cstride, d.det_counts, d.det_cap, d.det_thr, d.out_cstride = _NEVER_READ, 6, _NEVER_READ, 4096, 0.5, 4096
+    return d
 
 
 def conv_kernel_name(pc, H, W, bits=False, N=1):
     """Name of the kernel v2x_conv2d launches for layer pc on N maps of H x W (the layer's full-resolution input extent), as rocprofv3 prints it:
-    asked of the library's own dispatch (v2x_conv2d_plan), nothing is launched.  The activations and the output are 16-byte aligned placeholders: the
-    answer is the one for aligned tensors (a misaligned 1x1 launch takes the gather kernel; conv2d's profiling branch asks with its real descriptor)."""
-    d = _conv_desc(pc, N, H, W)
-    d.in0, d.in1, d.out = _NEVER_READ, (_NEVER_READ if pc.C1 else None), _NEVER_READ
-    if bits:
-        d.in_format, d.in_zbits = 1, 1
-    d.out_cstride = pc.Cout2 or pc.Cout
+    asked of the library's own dispatch (v2x_conv2d_plan), nothing is launched.  Every tensor is a 16-byte aligned placeholder: the answer
+    is the one for aligned tensors (a misaligned 1x1 launch takes the gather kernel; conv2d's profiling branch asks with its real descriptor)."""
+    d = _plan_desc(pc, N, H, W, bits)
     d.small_batch = 1 if latency_launches() else 0
     return _lib.conv_plan(d, "v2x_conv2d_plan(%s)" % pc.name)
+
+
+def covers(pc, H, W, bits=False):
+    """Has v2x_conv2d a kernel for layer pc on maps of H x W (bits: on the voxelizer's bit grid)?  The library's own dispatch answers; the
+    boolean is kept on the packing -- never a kernel name, which follows the switches, the number of maps and the latency declaration (the covered
+    set follows none: tests/test_coverage_cpu.py).  A refusal's text stays in v2x_last_error; _lib.check re-reads it after its own failing call."""
+    hit = pc.covered.get((H, W, bits))
+    if hit is None:
+        buf = C.create_string_buffer(512)
+        hit = pc.covered[(H, W, bits)] = _lib.load().v2x_conv2d_plan(C.byref(_plan_desc(pc, 1, H, W, bits)), buf, len(buf)) == 0
+    return hit
+
+
+@functools.lru_cache(maxsize=None)
+def wgrad_covers(H, W, cin, cout):
+    """Has v2x_conv3x3_wgrad a kernel for cin -> cout channels on maps of H x W?  The library's answer (a workspace slot count of 0: no), kept."""
+    return _lib.load().v2x_conv3x3_wgrad_splits(1, H, W, cin, cout) != 0
 
 
 # ------------------------------------------------------------------ a1
@@ -224,11 +260,13 @@ class PackedConv:
 
     __slots__ = ("weight", "scale", "shift", "C0", "C1", "Cout", "ksize", "stride", "pad", "up0", "epilogue", "relu",
                  "w_rows", "w_kpad", "name", "w_layout", "Cout2", "weight2", "scale2", "shift2", "relu2",
-                 "repack")   # packing.pack_conv_device: what packing.RepackPlan needs to rebuild `weight` in place (None otherwise)
+                 "repack",   # packing.pack_conv_device: what packing.RepackPlan needs to rebuild `weight` in place (None otherwise)
+                 "covered")  # covers(): {(H, W, bits): v2x_conv2d has a kernel for this packing at that extent}
 
     def __init__(self, **kw):
         for k in self.__slots__:
             setattr(self, k, kw.get(k))
+        self.covered = {}
 
 
 def conv_out_hw(pc, H, W):
@@ -593,9 +631,9 @@ def seg_argmax_confusion(logits, label=None, want_pred=True):
 
 # ------------------------------------------------------------------ layer = halo kernel when eligible, else gather kernel(s)
 class Layer:
-    """One logical layer (possibly a fused pair).  `halo` is the k-slot-major packing for
-    conv_halo.hip (3x3 stride 1, H % 8 == 0, W % 32 == 0); `fallback` is the list of gather-kernel
-    convs computing the same thing for any other extent.  `split` > 0: two output tensors."""
+    """One logical layer (possibly a fused pair).  `halo` is the packing of the patch-based kernel family that
+    covers the layer (conv_halo.hip, conv_stream*.hip) at the extents it tiles (covers()); `fallback` is the list
+    of gather-kernel convs computing the same thing for any other extent.  `split` > 0: two output tensors."""
 
     __slots__ = ("halo", "fallback", "split", "name", "det", "latency")
 
@@ -618,7 +656,7 @@ def small_batch_splitk(pc, N, H, W):
     chunks divided over `splitk` workgroups per tile (partial sums added by splitk_reduce_kernel in range order) the same layer runs on
     ~240.  The mode is DECLARED by the caller, never derived from the batch inside a sharded runner: the split changes the fp32 summation
     order (one bf16 rounding of the output), and kernel selection that followed the item count would break the R-rank == 1-rank bitwise
-    equality."""
+    equality.  Asked of a packing that covers(pc, H, W): select() is the caller."""
     if pc.w_layout != 2 or pc.stride not in (1, 2) or not latency_launches():
         return 0
     rows = _lib.load().v2x_conv_stream_tile_rows(pc.Cout, pc.epilogue)
@@ -629,25 +667,17 @@ def small_batch_splitk(pc, N, H, W):
         # conv1_1 (one chunk, resident form) and conv2_1 (two chunks) are never split
         if pc.C1 or pc.up0 or pc.Cout2 or pc.epilogue != V2X_EPI_BF16 or pc.w_rows != pc.Cout:
             return 0
-        if not ((H % 8 == 0 and W % 64 == 0) or (H % 16 == 0 and W % 32 == 0)):
-            return 0
         tiles = N * ((H // 2) * (W // 2) // 128) * (pc.Cout // rows)
-        chunks = pc.C0 // 32
-        if tiles >= _splitk_gate() or chunks < 8:                 # (conv3_1, 4 chunks: two ranges + the reduce launch 21 us against 20 unsplit)
+        chunks, least = pc.C0 // 32, 8                            # (conv3_1, 4 chunks: two ranges + the reduce launch 21 us against 20 unsplit)
+    else:
+        # Measured (one frame = 5 maps / eight = 40, tools/layer_profile.py): a split pays when the unsplit launch has fewer than ~200 tiles
+        # AND every range keeps >= 2 chunks (conv6_2, 4 chunks: 4 ranges of one 35 us vs 32 unsplit); the 4-wave kernel WITHOUT a split is slower
+        # than the 8-wave forms even at 160 workgroups (conv5_1 at 40 maps: 163 vs 137 us), so there is no "more, smaller tiles" mode.
+        if pc.Cout2:
             return 0
-        want = min(chunks // 2, -(-(getattr(_latency, "target", 0) or tuning.get("SPLITK_TARGET")) // tiles))
-        while want > 1 and -(-chunks // want) * (want - 1) >= chunks:
-            want -= 1
-        return want if want > 1 else 0
-    t16 = W % 32 != 0
-    if (t16 and (W % 16 or H % 16)) or (not t16 and H % 8):
-        return 0
-    tiles = N * (H * W // 256) * (pc.w_rows // rows)       # workgroups of the 4-wave form (256-pixel tiles)
-    chunks = (pc.C0 + pc.C1) // 32
-    # Measured (one frame = 5 maps / eight = 40, tools/layer_profile.py): a split pays when the unsplit launch has fewer than ~200 tiles
-    # AND every range keeps >= 2 chunks (conv6_2, 4 chunks: 4 ranges of one 35 us vs 32 unsplit); the 4-wave kernel WITHOUT a split is slower
-    # than the 8-wave forms even at 160 workgroups (conv5_1 at 40 maps: 163 vs 137 us), so there is no "more, smaller tiles" mode.
-    if pc.Cout2 or tiles >= _splitk_gate() or chunks < 4:
+        tiles = N * (H * W // 256) * (pc.w_rows // rows)       # workgroups of the 4-wave form (256-pixel tiles)
+        chunks, least = (pc.C0 + pc.C1) // 32, 4
+    if tiles >= _splitk_gate() or chunks < least:
         return 0
     want = min(chunks // 2, -(-(getattr(_latency, "target", 0) or tuning.get("SPLITK_TARGET")) // tiles))
     while want > 1 and -(-chunks // want) * (want - 1) >= chunks:     # no empty range
@@ -655,49 +685,35 @@ def small_batch_splitk(pc, N, H, W):
     return want if want > 1 else 0
 
 
-def halo_eligible(H, W, w_layout=1, cmax=0, cout=0):
-    """cmax: the widest source's channel count -- the halo kernel's packed DMA tables hold a lane's element offset inside the patch rows
-    in 20 bits (conv_halo.hip: (10 W + 34) cmax < 2^20, i.e. W < 1 635 at 64 channels); wider maps take the layer's fallback."""
-    if w_layout in (1, 3) and (10 * W + 34) * cmax >= (1 << 20):
-        return False
-    if w_layout == 4:
-        return H % 16 == 0 and W % (64 if cout == 64 else 32) == 0      # the streamed parity-class kernels: 16 x 32 tiles (pairs of them at 64 rows)
-    if H % 8 == 0 and W % 32 == 0:
-        return True
-    return w_layout == 2 and H % 16 == 0 and W % 16 == 0  # the streamed kernel also has 16x16 tiles
+def select(layer, N, H, W, bits=False):
+    """-> (the packing run_layer launches for N maps of H x W, its splitk), or None: the gather fallback chain.  Which extents a kernel family
+    tiles is the library's answer (covers); the policy is Python's: the bit grid (bits) goes only to a halo packing; inside a declared latency
+    block `layer.latency` is taken when small_batch_splitk splits it; the streamed stride-1 forms (one 256-pixel tile per workgroup) run from
+    256 pixels per map on.  That choice looks at the map extent only, never at the batch: kernel selection must not change with the number of
+    items a rank owns, or R-rank results would stop being bitwise equal to 1-rank results."""
+    h = layer.halo
+    if bits:
+        return (h, 0) if h is not None and h.w_layout == 1 and covers(h, H, W, True) else None
+    lat = layer.latency
+    if lat is not None and latency_launches() and covers(lat, H, W):
+        sk = small_batch_splitk(lat, N, H, W)
+        if sk > 1:
+            return lat, sk
+    if h is None or not covers(h, H, W) or (h.w_layout in (2, 4) and h.stride == 1 and H * W < 256):
+        return None
+    return h, small_batch_splitk(h, N, H, W)
 
 
 def run_layer(layer, in0, in1=None, zbits=0):
     """zbits > 0: in0 is the voxelizer's int32 bit grid (N, H, W) -- only the first layer's halo packing reads it."""
-    if in0.dtype == torch.int32:
-        h = layer.halo
-        if h is None or not halo_eligible(in0.shape[1], in0.shape[2], 1) or h.w_layout != 1:
-            in0 = bits_to_nhwc(in0, zbits, layer.fallback[0].C0)  # odd extent: expand, then the gather kernel
-        else:
-            return conv2d(h, in0, zbits=zbits)
-    if in1 is not None:
-        H, W = in1.shape[1], in1.shape[2]
-    else:
-        H, W = in0.shape[1], in0.shape[2]
-    h = layer.halo
-    if layer.latency is not None and latency_launches():
-        sk = small_batch_splitk(layer.latency, in0.shape[0], H, W)
-        if sk > 1:
-            return conv2d(layer.latency, in0, in1, split=layer.split, splitk=sk)
-    if h is not None and h.stride == 2:
-        # stride-2 streamed kernel: 4x32 output tiles, or 8x16 ones for narrow maps (conv4_1: 16x16 outputs)
-        if (H % 8 == 0 and W % 64 == 0) or (H % 16 == 0 and W % 32 == 0):
-            return conv2d(h, in0, in1, split=layer.split, splitk=small_batch_splitk(h, in0.shape[0], H, W))
-    elif h is not None and halo_eligible(H, W, h.w_layout, max(h.C0, h.C1 or 0), h.Cout):
-        use = True
-        if h.w_layout in (2, 4):
-            # streamed kernel = one 256-pixel x <=128-channel tile per workgroup.  The choice looks at the map extent
-            # only, never at the batch: kernel selection must not change with the number of items a rank owns, or
-            # R-rank results would stop being bitwise equal to 1-rank results.  16x16 maps give Cout/128 workgroups
-            # per map, enough to fill 256 CUs from ~13 frames x 5 agents on; below 16x16 the gather kernel is used.
-            use = H * W >= 256
-        if use:
-            return conv2d(h, in0, in1, split=layer.split, splitk=small_batch_splitk(h, in0.shape[0], H, W))
+    src = in0 if in1 is None else in1
+    N, H, W = in0.shape[0], src.shape[1], src.shape[2]
+    sel = select(layer, N, H, W, in0.dtype == torch.int32)
+    if sel is None and in0.dtype == torch.int32:
+        in0 = bits_to_nhwc(in0, zbits, layer.fallback[0].C0)  # no kernel reads the bit grid at this extent: expand, then as any bf16 map
+        sel = select(layer, N, H, W)
+    if sel is not None:
+        return conv2d(sel[0], in0, in1, split=layer.split, zbits=zbits, splitk=sel[1])
     y = conv2d(layer.fallback[0], in0, in1, split=layer.split if len(layer.fallback) == 1 else 0)
     for i, pc in enumerate(layer.fallback[1:], 1):
         y = conv2d(pc, y, split=layer.split if i == len(layer.fallback) - 1 else 0)

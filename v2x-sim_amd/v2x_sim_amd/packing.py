@@ -315,44 +315,86 @@ class RepackPlan:
                 i["shift"][:i["cout"]].copy_(i["bias"]().detach())
 
 
+def _spec_shape(name, spec, **fields):
+    """-> (a PackedConv WITHOUT tensors, the packed buffer's bytes, spec): every descriptor field of the layer the spec packs -- w_rows and
+    w_kpad are v2x_pack_conv_size's answer -- with no activation, as the training graph runs its layers.  Enough for ops.covers;
+    _pack_device(*this, ...) adds the tensors."""
+    import ctypes as C
+    lib = _lib.load()
+    rows, kpad = C.c_int32(0), C.c_int32(0)
+    nbytes = lib.v2x_pack_conv_size(C.byref(spec), C.byref(rows), C.byref(kpad))
+    if nbytes == 0:
+        raise ValueError("%s: %s" % (name, lib.v2x_last_error().decode()))
+    k = spec.ksize
+    return PackedConv(name=name, Cout=spec.Cout, ksize=k, pad=k // 2, epilogue=spec.epilogue, relu=False, w_rows=rows.value, w_kpad=kpad.value,
+                      w_layout=spec.w_layout or None, Cout2=0, **fields), nbytes, spec
+
+
+def _pack_device(pc, nbytes, spec, weight, dgrad, bias):
+    """The one-launch device packing (v2x_pack_conv_device) behind pack_conv_device / pack_conv_device_halo / pack_conv1x1_device: fills
+    _spec_shape's PackedConv with the packed buffer (dgrad: packed from the flipped, transposed weights; no bias), the shared scale vector,
+    shift = the bias, and the `repack` record."""
+    import ctypes as C
+    w = weight.detach()
+    if w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous():
+        w = w.float().contiguous()
+    buf = torch.empty((nbytes // 2,), dtype=torch.bfloat16, device=w.device)
+    _lib.check(_lib.load().v2x_pack_conv_device(C.byref(spec), C.c_void_p(w.data_ptr()), 1 if dgrad else 0, C.c_void_p(buf.data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "v2x_pack_conv_device(%s)" % pc.name)
+    n_par, cout = pc.w_rows, pc.Cout
+    if dgrad:
+        bias = None
+    pc.weight = buf
+    pc.scale = _const(n_par, 1.0, w.device, cout)     # shared read-only vectors: no fill per packing (ones for the real rows, zeros for the padding)
+    if bias is None:
+        pc.shift = _const(n_par, 0.0, w.device)
+    elif n_par == cout and bias.dtype == torch.float32:
+        pc.shift = bias.detach()                       # the parameter itself (the packing lives until its next update)
+    else:
+        pc.shift = torch.zeros((n_par,), dtype=torch.float32, device=w.device)
+        pc.shift[:cout] = bias.detach().float()
+    pc.repack = _repack_info(spec, weight, w, dgrad, buf, pc.shift, bias, cout)
+    return pc
+
+
+def train_conv_shape(name, cin, cout, stride=1, cin_pad=None):
+    """The training graph's plain 3x3 layer cin -> cout BEFORE it is packed -> (a PackedConv without tensors, the buffer's bytes, the
+    v2x_pack_spec): the kernel family train_layout picks, w_rows / w_kpad from v2x_pack_conv_size.  No device is touched: hip_graph.hip_eligible
+    asks ops.select about it; pack_conv_device packs it."""
+    from ._lib import PackSpec
+    cin_p = cin if cin_pad is None else cin_pad
+    spec = PackSpec(Cout=cout, Cin=cin, ksize=3, cin_pad=cin_p, w_layout=train_layout(cin_p, cout, stride), epilogue=V2X_EPI_BF16, chain=0)
+    return _spec_shape(name, spec, C0=cin_p, C1=0, stride=stride, up0=0)
+
+
+def as_layer(pc):
+    """The ops.Layer of a training-graph packing: the gather packing as the layer's `fallback`, any other as its `halo` (no fallback beside it)."""
+    from .ops import Layer
+    return Layer([], pc, name=pc.name) if pc.w_layout else Layer([pc], None, name=pc.name)
+
+
 def pack_conv_device(name, weight, bias, *, stride=1, cin_pad=None, dgrad=False):
     """One-launch device packing of a plain 3x3 layer for the training graph (v2x_pack_conv_device): weight = the fp32 parameter ON THE
     DEVICE, [Cout, Cin, 3, 3].  dgrad: the layer that computes the convolution's data gradient (stride-1 convolution of dy with the flipped,
     transposed weights, no bias).  -> ops.Layer carrying exactly ONE packing (the kernel family train_layout picks; the gather packing
     as the layer's `fallback`, the others as its `halo`), scale = 1, shift = bias."""
-    import ctypes as C
-    from ._lib import PackSpec
-    from .ops import Layer
-    lib = _lib.load()
-    w = weight.detach()
-    if w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous():
-        w = w.float().contiguous()
-    co_w, ci_w = w.shape[0], w.shape[1]
-    cout, cin = (ci_w, co_w) if dgrad else (co_w, ci_w)
-    cin_p = cin if cin_pad is None else cin_pad
-    layout = train_layout(cin_p, cout, 1 if dgrad else stride)
-    spec = PackSpec(Cout=cout, Cin=cin, ksize=3, cin_pad=cin_p, w_layout=layout, epilogue=V2X_EPI_BF16, chain=0)
-    rows, kpad = C.c_int32(0), C.c_int32(0)
-    nbytes = lib.v2x_pack_conv_size(C.byref(spec), C.byref(rows), C.byref(kpad))
-    if nbytes == 0:
-        raise ValueError("pack_conv_device(%s): %s" % (name, lib.v2x_last_error().decode()))
-    buf = torch.empty((nbytes // 2,), dtype=torch.bfloat16, device=w.device)
-    _lib.check(lib.v2x_pack_conv_device(C.byref(spec), C.c_void_p(w.data_ptr()), 1 if dgrad else 0, C.c_void_p(buf.data_ptr()),
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "v2x_pack_conv_device(%s)" % name)
-    n_par = rows.value
-    scale = _const(n_par, 1.0, w.device, cout)        # shared read-only vectors: no fill per packing (ones for the real rows, zeros for the padding)
-    if bias is not None and not dgrad:
-        if n_par == cout and bias.dtype == torch.float32:
-            shift = bias.detach()                      # the parameter itself (the packing lives until its next update)
-        else:
-            shift = torch.zeros((n_par,), dtype=torch.float32, device=w.device)
-            shift[:cout] = bias.detach().float()
+    co_w, ci_w = weight.shape[0], weight.shape[1]
+    if dgrad:
+        shape = train_conv_shape(name, co_w, ci_w, 1, cin_pad)
     else:
-        shift = _const(n_par, 0.0, w.device)
-    pc = PackedConv(name=name, weight=buf, scale=scale, shift=shift, C0=cin_p, C1=0, Cout=cout, ksize=3, stride=1 if dgrad else stride, pad=1,
-                    up0=0, epilogue=V2X_EPI_BF16, relu=False, w_rows=n_par, w_kpad=kpad.value, w_layout=layout or None, Cout2=0)
-    pc.repack = _repack_info(spec, weight, w, dgrad, buf, shift, bias, cout)
-    return Layer([pc], None, name=name) if layout == 0 else Layer([], pc, name=name)
+        shape = train_conv_shape(name, ci_w, co_w, stride, cin_pad)
+    return as_layer(_pack_device(*shape, weight, dgrad, bias))
+
+
+def halo_conv_shape(name, co_w, ci_w, c_up=0, dgrad_rows=None):
+    """pack_conv_device_halo's layer for a [co_w, ci_w, 3, 3] parameter before it is packed: as train_conv_shape."""
+    from ._lib import PackSpec
+    if dgrad_rows is None:
+        spec = PackSpec(Cout=co_w, Cin=ci_w, ksize=3, cin_pad=ci_w, w_layout=1, epilogue=V2X_EPI_BF16, chain=0)
+        return _spec_shape(name, spec, C0=c_up, C1=ci_w - c_up, stride=1, up0=1 if c_up else 0)
+    r0, n = dgrad_rows
+    spec = PackSpec(Cout=n, Cin=co_w, ksize=3, cin_pad=co_w, w_layout=1, epilogue=V2X_EPI_BF16, chain=0, src_rows=ci_w, src_row0=r0)
+    return _spec_shape(name, spec, C0=co_w, C1=0, stride=1, up0=0)
 
 
 def pack_conv_device_halo(name, weight, bias, *, c_up=0, dgrad_rows=None):
@@ -363,42 +405,7 @@ def pack_conv_device_halo(name, weight, bias, *, c_up=0, dgrad_rows=None):
       * dgrad_rows=(r0, n): the DATA-GRADIENT layer of the input channels r0 .. r0 + n - 1 alone (Cout -> n channels; v2x_pack_spec.src_rows / src_row0): the
         32 -> 96 data gradient has no halo kernel (conv_halo.hip: it spills), 32 -> 64 and 32 -> 32 into one 96-channel map have.
     -> PackedConv."""
-    import ctypes as C
-    from ._lib import PackSpec
-    lib = _lib.load()
-    w = weight.detach()
-    if w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous():
-        w = w.float().contiguous()
-    co_w, ci_w = w.shape[0], w.shape[1]
-    if dgrad_rows is None:
-        spec = PackSpec(Cout=co_w, Cin=ci_w, ksize=3, cin_pad=ci_w, w_layout=1, epilogue=V2X_EPI_BF16, chain=0)
-        cout, c0, c1, up0 = co_w, c_up, ci_w - c_up, 1 if c_up else 0
-    else:
-        r0, n = dgrad_rows
-        spec = PackSpec(Cout=n, Cin=co_w, ksize=3, cin_pad=co_w, w_layout=1, epilogue=V2X_EPI_BF16, chain=0, src_rows=ci_w, src_row0=r0)
-        cout, c0, c1, up0 = n, co_w, 0, 0
-    rows, kpad = C.c_int32(0), C.c_int32(0)
-    nbytes = lib.v2x_pack_conv_size(C.byref(spec), C.byref(rows), C.byref(kpad))
-    if nbytes == 0:
-        raise ValueError("pack_conv_device_halo(%s): %s" % (name, lib.v2x_last_error().decode()))
-    buf = torch.empty((nbytes // 2,), dtype=torch.bfloat16, device=w.device)
-    dgrad = dgrad_rows is not None
-    _lib.check(lib.v2x_pack_conv_device(C.byref(spec), C.c_void_p(w.data_ptr()), 1 if dgrad else 0, C.c_void_p(buf.data_ptr()),
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "v2x_pack_conv_device(%s)" % name)
-    n_par = rows.value
-    scale = _const(n_par, 1.0, w.device, cout)
-    if bias is not None and not dgrad:
-        if n_par == cout and bias.dtype == torch.float32:
-            shift = bias.detach()
-        else:
-            shift = torch.zeros((n_par,), dtype=torch.float32, device=w.device)
-            shift[:cout] = bias.detach().float()
-    else:
-        shift = _const(n_par, 0.0, w.device)
-    pc = PackedConv(name=name, weight=buf, scale=scale, shift=shift, C0=c0, C1=c1, Cout=cout, ksize=3, stride=1, pad=1, up0=up0,
-                    epilogue=V2X_EPI_BF16, relu=False, w_rows=n_par, w_kpad=kpad.value, w_layout=1, Cout2=0)
-    pc.repack = _repack_info(spec, weight, w, dgrad, buf, shift, bias if not dgrad else None, cout)
-    return pc
+    return _pack_device(*halo_conv_shape(name, weight.shape[0], weight.shape[1], c_up, dgrad_rows), weight, dgrad_rows is not None, bias)
 
 
 def pack_conv1x1_device(name, weight, bias, *, dgrad=False, cout_pad=0, f32_out=False):
@@ -406,40 +413,15 @@ def pack_conv1x1_device(name, weight, bias, *, dgrad=False, cout_pad=0, f32_out=
     DEVICE, [Cout, Cin, 1, 1] (or [Cout, Cin]).  dgrad: the layer dx = dy . W (the transposed weights; dy's channels zero-padded to cout_pad, no
     bias, bf16 output).  -> PackedConv with scale = 1, shift = bias -- the bytes of the torch-op packing it replaces (pad / transpose / cast /
     scatter into a zeroed buffer: ~8 small launches per packing, 8 packings per training step)."""
-    import ctypes as C
     from ._lib import PackSpec
-    from ._lib import V2X_EPI_F32
-    lib = _lib.load()
-    w = weight.detach()
-    if w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous():
-        w = w.float().contiguous()
-    co_w, ci_w = w.shape[0], w.shape[1]
+    co_w, ci_w = weight.shape[0], weight.shape[1]
     if dgrad:
         cout, cin, cin_p = ci_w, co_w, max(cout_pad, co_w)
     else:
         cout, cin, cin_p = co_w, ci_w, ci_w
-    epi = V2X_EPI_F32 if (f32_out and not dgrad) else V2X_EPI_BF16
-    spec = PackSpec(Cout=cout, Cin=cin, ksize=1, cin_pad=cin_p, w_layout=0, epilogue=epi, chain=0)
-    rows, kpad = C.c_int32(0), C.c_int32(0)
-    nbytes = lib.v2x_pack_conv_size(C.byref(spec), C.byref(rows), C.byref(kpad))
-    if nbytes == 0:
-        raise ValueError("pack_conv1x1_device(%s): %s" % (name, lib.v2x_last_error().decode()))
-    buf = torch.empty((nbytes // 2,), dtype=torch.bfloat16, device=w.device)
-    _lib.check(lib.v2x_pack_conv_device(C.byref(spec), C.c_void_p(w.data_ptr()), 1 if dgrad else 0, C.c_void_p(buf.data_ptr()),
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "v2x_pack_conv_device(%s)" % name)
-    n_par = rows.value
-    scale = _const(n_par, 1.0, w.device, cout)
-    if bias is not None and not dgrad:
-        if n_par == cout and bias.dtype == torch.float32:
-            shift = bias.detach()
-        else:
-            shift = torch.zeros((n_par,), dtype=torch.float32, device=w.device)
-            shift[:cout] = bias.detach().float()
-    else:
-        shift = _const(n_par, 0.0, w.device)
-    pc = PackedConv(name=name, weight=buf.view(n_par, kpad.value), scale=scale, shift=shift, C0=cin_p, C1=0, Cout=cout, ksize=1, stride=1, pad=0,
-                    up0=0, epilogue=epi, relu=False, w_rows=n_par, w_kpad=kpad.value)
-    pc.repack = _repack_info(spec, weight, w, dgrad, buf, shift, bias if not dgrad else None, cout)
+    spec = PackSpec(Cout=cout, Cin=cin, ksize=1, cin_pad=cin_p, w_layout=0, epilogue=V2X_EPI_F32 if (f32_out and not dgrad) else V2X_EPI_BF16, chain=0)
+    pc = _pack_device(*_spec_shape(name, spec, C0=cin_p, C1=0, stride=1, up0=0), weight, dgrad, bias)
+    pc.weight = pc.weight.view(pc.w_rows, pc.w_kpad)
     return pc
 
 

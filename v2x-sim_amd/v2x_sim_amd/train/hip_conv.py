@@ -24,8 +24,8 @@ from .._lib import V2X_EPI_BF16
 
 def eligible(weight, stride, padding, H, W):
     cout, cin, kh, kw = weight.shape
-    return (kh == 3 and kw == 3 and tuple(stride) == (1, 1) and tuple(padding) == (1, 1) and cin % 32 == 0 and cout % 64 == 0
-            and cin >= 32 and H % 8 == 0 and W % 32 == 0)
+    return (kh == 3 and kw == 3 and tuple(stride) == (1, 1) and tuple(padding) == (1, 1) and cout % 64 == 0 and cin >= 32
+            and ops.wgrad_covers(H, W, cin, cout))
 
 
 def _pack_plain(name, w, bias, device):

@@ -23,6 +23,7 @@ Mixed precision: activations, activation gradients and the MFMA operands are bf1
 gradients and the master weights are fp32.  Enabled with V2X_TRAIN_HIP=1 (FaFModule.step / train_forward); there is no CPU path.
 """
 import contextlib
+import functools
 import types
 import weakref
 
@@ -49,20 +50,25 @@ def _versions(weight, bias):
     return (packing.param_version(weight), None if bias is None else packing.param_version(bias))
 
 
-def _layer(kind, weight, bias, stride, cin_pad):
-    # keyed on the parameter OBJECT (weak reference checked on a hit): a data_ptr can be reused by another model's tensor
-    key = (kind, id(weight), stride, cin_pad)
+def _cached(key, weight, bias, pack):
+    """pack() -- one device launch per packing (v2x_pack_conv_device) -- kept until the parameter changes.  key holds id(weight): the parameter
+    OBJECT (weak reference checked on a hit), a data_ptr can be reused by another model's tensor."""
     ver = _versions(weight, bias)
     hit = _CACHE.get(key)
     if hit is not None and hit[0] == ver and hit[2]() is weight:
         return hit[1]
-    # one device launch per packing (v2x_pack_conv_device); the data gradient = a stride-1 convolution with the flipped, transposed weights
-    layer = packing.pack_conv_device("train." + kind, weight, bias, stride=stride, cin_pad=cin_pad, dgrad=kind == "dgrad")
     if len(_CACHE) > 512:
         _CACHE.clear()
         _PLANS.clear()
-    _CACHE[key] = (ver, layer, weakref.ref(weight), None if bias is None else weakref.ref(bias))
-    return layer
+    packed = pack()
+    _CACHE[key] = (ver, packed, weakref.ref(weight), None if bias is None else weakref.ref(bias))
+    return packed
+
+
+def _layer(kind, weight, bias, stride, cin_pad):
+    """The forward layer, or (kind "dgrad") the data gradient = a stride-1 convolution with the flipped, transposed weights."""
+    return _cached((kind, id(weight), stride, cin_pad), weight, bias,
+                   lambda: packing.pack_conv_device("train." + kind, weight, bias, stride=stride, cin_pad=cin_pad, dgrad=kind == "dgrad"))
 
 
 # After an optimizer step EVERY cached packing is stale (~55 per model: forward and data-gradient layers).  Re-packed lazily, one launch each, that
@@ -136,28 +142,26 @@ def _zero_insert(dy):
     return z
 
 
-def _layer_runs(cin_p, cout, stride, H, W):
-    """Will ops.run_layer find a kernel for the ONE packing packing.pack_conv_device makes for this layer (it packs no gather fallback beside
-    a halo / streamed layout)?  Mirrors run_layer's conditions exactly (a miss there is an IndexError on the empty fallback list)."""
-    layout = packing.train_layout(cin_p, cout, stride)
-    if layout == 0:
-        return True                                    # the gather kernel takes any extent
-    if stride == 2:
-        return (H % 8 == 0 and W % 64 == 0) or (H % 16 == 0 and W % 32 == 0)
-    return ops.halo_eligible(H, W, layout, cin_p) and (layout != 2 or H * W >= 256)
+def _selects(cin, cout, stride, H, W):
+    """ops.run_layer finds a kernel for the ONE packing packing.pack_conv_device makes for this layer (it packs no gather fallback beside a
+    halo / streamed layout: ADVICE r3, a miss there is an IndexError on the empty fallback list) -- asked of ops.select itself, on the layer's
+    descriptor fields before anything is packed."""
+    layer = packing.as_layer(packing.train_conv_shape("train", cin, cout, stride)[0])
+    return layer.halo is None or ops.select(layer, 1, H, W) is not None       # (the gather kernel takes any extent)
+
+
+@functools.lru_cache(maxsize=None)     # (a step asks about ~20 keys, over and over)
+def _kernels_cover(cin_p, cout, stride, H, W):
+    return ops.wgrad_covers(H, W, cin_p, cout) and _selects(cin_p, cout, stride, H, W) and _selects(cout, cin_p, 1, H, W)
 
 
 def hip_eligible(weight, stride, H, W, cin_pad=None):
-    """3x3, stride 1 or 2, pad 1, Cout % 32 == 0 (Cin is padded to 32), and every launch of the layer's forward AND backward has a kernel at
-    this extent: the forward layer, the data-gradient layer (a stride-1 convolution Cout -> Cin' at the input extent) and the weight-gradient
-    kernel (H % 8 == 0, W % 32 == 0).  Anything else takes the F.conv2d path of conv3x3()."""
+    """3x3, stride 1 or 2, pad 1 (Cin is padded to a whole channel tile), and every launch of the layer's forward AND backward has a kernel at
+    this extent: the weight-gradient kernel, the forward layer and the data-gradient layer (a stride-1 convolution Cout -> Cin' at the input
+    extent).  Anything else takes the F.conv2d path of conv3x3()."""
     cout, cin, kh, kw = weight.shape
-    if not (kh == 3 and kw == 3 and stride in (1, 2) and cout % 32 == 0 and H % 8 == 0 and W % 32 == 0):
-        return False
     cin_p = cin_pad if cin_pad is not None else (cin + 31) // 32 * 32
-    if cin_p % 32:
-        return False
-    return _layer_runs(cin_p, cout, stride, H, W) and _layer_runs(cout, cin_p, 1, H, W)
+    return kh == 3 and kw == 3 and stride in (1, 2) and _kernels_cover(cin_p, cout, stride, H, W)
 
 
 def _run_layer(layer, x):
@@ -313,16 +317,10 @@ def cbr(x, conv, bn):
 
 
 def _layer_1x1(kind, weight, bias, f32_out, cout_pad):
-    key = (kind, id(weight), f32_out, cout_pad)
-    ver = (packing.param_version(weight), None if bias is None else packing.param_version(bias))
-    hit = _CACHE.get(key)
-    if hit is not None and hit[0] == ver and hit[2]() is weight:
-        return hit[1]
-    # one device launch per packing (v2x_pack_conv_device, gather layout); dgrad: dx = dy . W, the gradient's channels zero-padded to cout_pad
-    pc = packing.pack_conv1x1_device("train." + kind + "1x1", weight, bias if kind == "fwd" else None, dgrad=kind != "fwd", cout_pad=cout_pad,
-                                     f32_out=f32_out)
-    _CACHE[key] = (ver, pc, weakref.ref(weight), None if bias is None else weakref.ref(bias))
-    return pc
+    # gather layout; dgrad: dx = dy . W, the gradient's channels zero-padded to cout_pad
+    return _cached((kind, id(weight), f32_out, cout_pad), weight, bias,
+                   lambda: packing.pack_conv1x1_device("train." + kind + "1x1", weight, bias if kind == "fwd" else None, dgrad=kind != "fwd",
+                                                       cout_pad=cout_pad, f32_out=f32_out))
 
 
 class _Conv1x1(torch.autograd.Function):
@@ -368,7 +366,7 @@ class _Conv1x1(torch.autograd.Function):
 def conv1x1(x, weight, bias, f32_out=False):
     """1x1 layer (nn.Conv2d 1x1 or upstream's Conv3D 1x1x1 on a length-1 sequence) on a bf16 NHWC map."""
     N, H, W, cin = x.shape
-    if H % 8 == 0 and W % 32 == 0 and cin % 32 == 0:
+    if ops.wgrad_covers(H, W, cin, (weight.shape[0] + 31) // 32 * 32):      # (the weight gradient reads dy with its channels padded to 32)
         return _Conv1x1.apply(x.contiguous(), weight, bias, f32_out)
     y = F.linear(x.float(), weight.reshape(weight.shape[0], weight.shape[1]), bias)      # odd extent: the library GEMM
     return y if f32_out else y.to(BF16)
@@ -395,14 +393,8 @@ class _UpCat(torch.autograd.Function):
 
 def _layer_halo(kind, weight, bias, c_up, rows):
     """Cached halo packings of the decoder's full-resolution `_1` layer (packing.pack_conv_device_halo): kind "up8.fwd" | "up8.dA" | "up8.dB"."""
-    key = (kind, id(weight), c_up, rows)
-    ver = _versions(weight, bias)
-    hit = _CACHE.get(key)
-    if hit is not None and hit[0] == ver and hit[2]() is weight:
-        return hit[1]
-    pc = packing.pack_conv_device_halo("train." + kind, weight, bias, c_up=c_up, dgrad_rows=rows)
-    _CACHE[key] = (ver, pc, weakref.ref(weight), None if bias is None else weakref.ref(bias))
-    return pc
+    return _cached((kind, id(weight), c_up, rows), weight, bias,
+                   lambda: packing.pack_conv_device_halo("train." + kind, weight, bias, c_up=c_up, dgrad_rows=rows))
 
 
 class _UpCatConv3x3(torch.autograd.Function):
@@ -443,11 +435,20 @@ class _UpCatConv3x3(torch.autograd.Function):
         return d_lo, d_skip, dw, db
 
 
+@functools.lru_cache(maxsize=None)
+def upcat_conv_covered(H, W):
+    """_UpCatConv3x3's three halo launches -- forward 64 + 32 -> 32, data gradients 32 -> 64 and 32 -> 32 -- and its weight gradient all have a
+    kernel on full-resolution maps of H x W (a map too wide for the halo kernels' DMA tables has not: ADVICE r6)."""
+    shapes = (packing.halo_conv_shape("train.up8", 32, 96, c_up, rows)[0] for c_up, rows in ((64, None), (0, (0, 64)), (0, (64, 32))))
+    return ops.wgrad_covers(H, W, 96, 32) and all(ops.covers(pc, H, W) for pc in shapes)
+
+
 def upcat_conv3x3(lo, skip, conv):
-    """conv(cat(up(lo), skip)) -- the fused form where the halo kernels cover the shape (64 + 32 -> 32, H % 8 == 0, W % 32 == 0), else conv3x3(upcat(...))."""
+    """conv(cat(up(lo), skip)) -- the fused form where the halo kernels cover the shape (64 + 32 -> 32 at an extent upcat_conv_covered), else
+    conv3x3(upcat(...))."""
     N, H, W, C = lo.shape
     if (tuning.get("TRAIN_UPCAT_CONV") != 0 and (C, skip.shape[3], conv.weight.shape[0]) == (64, 32, 32) and conv.stride[0] == 1
-            and lo.dtype == BF16 and skip.dtype == BF16 and skip.shape[:3] == (N, 2 * H, 2 * W) and (2 * H) % 8 == 0 and (2 * W) % 32 == 0
+            and lo.dtype == BF16 and skip.dtype == BF16 and skip.shape[:3] == (N, 2 * H, 2 * W) and upcat_conv_covered(2 * H, 2 * W)
             and conv.weight.shape[1] == C + skip.shape[3] and conv.weight.is_cuda and conv.weight.dtype == torch.float32):
         return _UpCatConv3x3.apply(lo.contiguous(), skip.contiguous(), conv.weight, conv.bias)
     return conv3x3(upcat(lo, skip), conv)
@@ -514,7 +515,7 @@ def codec(e, x_3):
     and the BatchNorm kernel >= 8 channels, so both layers run on the library ops -- said once per shape, never silently."""
     cc = e.com_compresser.out_channels
     N, H, W, _ = x_3.shape
-    if cc % 32 == 0 and H % 8 == 0 and W % 32 == 0:
+    if ops.wgrad_covers(H, W, cc, cc):            # (conv1x1 asks for each layer's own channels; the message's cc are the ones that can miss)
         m = bn_relu(conv1x1(x_3, e.com_compresser.weight, e.com_compresser.bias), e.bn_compress)
         return bn_relu(conv1x1(m, e.com_decompresser.weight, e.com_decompresser.bias), e.bn_decompress)
     key = (cc, H, W)
@@ -747,7 +748,7 @@ def seg_head_loss(y, weight, bias, labels, class_weight=None, ignore_index=255):
     from .loss import seg_loss_weight, segmentation_loss
     N, H, W, cin = y.shape
     cout = weight.shape[0]
-    if (tuning.get("TRAIN_SEG_HEAD_FUSE") != 0 and tuning.get("TRAIN_SEG_LOSS_HIP") != 0 and y.dtype == BF16 and H % 8 == 0 and W % 32 == 0 and cin % 32 == 0
+    if (tuning.get("TRAIN_SEG_HEAD_FUSE") != 0 and tuning.get("TRAIN_SEG_LOSS_HIP") != 0 and y.dtype == BF16 and ops.wgrad_covers(H, W, cin, (cout + 31) // 32 * 32)
             and labels.dtype == torch.uint8 and labels.device == y.device and tuple(labels.shape) == (N, H, W) and ignore_index >= cout
             and ops.seg_loss_shape_ok(N * H * W, cout, (cout + 31) // 32 * 32)):
         return _SegHeadLoss.apply(y.contiguous(), weight, bias, labels.contiguous(), seg_loss_weight(class_weight, y))
