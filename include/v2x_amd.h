@@ -684,6 +684,44 @@ int v2x_seg_rasterize(const float *boxes, const uint8_t *cls, const int32_t *cou
                       int Y, int n_cls, const uint8_t *rank, uint8_t *labels, int32_t *owner, long long *hist, void *workspace,
                       long long workspace_bytes, v2x_stream_t stream);
 
+/* f-2 / f-3: synthetic scenes with occlusion -- the sweeps of all agents of all frames of a step ray-cast against a scene of boxes, compacted into the
+ * (points, n_pts) form v2x_voxelize_bits reads, with per-box return counts; v2x_lidar_visible_boxes turns the counts into each sweep's ground truth (the
+ * num_lidar_pts rule of the real data preparation).  DESIGN.md section 3.12 "LiDAR ray cast" is the frozen rule.  Two launches (one for the ground truth),
+ * no allocation, no host synchronisation, capturable; EVERY output element is written, the caller clears nothing; two calls give identical bytes.
+ * sensors fp32 [n_sweeps][6] (x, y, z, yaw, cos yaw, sin yaw); frame_of int32 [n_sweeps]: the sweep's frame (outside [0, n_frames): an empty scene).
+ * boxes fp32 [n_frames][box_cap][9] (cx, cy, w, h, yaw, cos yaw, sin yaw, z0, z1), w along the box's local x, h along its local y; box_count int32
+ *   [n_frames] (clamped to [0, box_cap]), box_cap in [1, 256].  A box with a non-finite field, a negative extent or z1 < z0 is dropped, keeping its index.
+ * beam fp32 [n_beams][2] (cos, sin of the elevation), az fp32 [n_az][2] (cos, sin of the azimuth): ray r = b * n_az + a; n_beams * n_az <= 2^24.  The
+ *   host passes every angle as its cos / sin pair: no trigonometric function is called for the geometry.
+ * Geometry in fp64 from the fp32 inputs, every product and sum rounded on its own: d = (ce*ca, ce*sa, se), world direction w = (c*dx - s*dy, s*dx + c*dy,
+ *   dz), origin o = (x, y, z).  Box g by slabs: px = ox - cx, py = oy - cy, lx = px*cg + py*sg, ly = -px*sg + py*cg, ux = wx*cg + wy*sg, uy = -wx*sg +
+ *   wy*cg; x in [-w/2, w/2], y in [-h/2, h/2], z in [z0, z1] with lz = oz, uz = dz; from t_near = -inf, t_far = +inf, per axis: u == 0: a miss when l
+ *   lies outside the closed slab, otherwise no constraint; u != 0: ta = (lo - l)/u, tb = (hi - l)/u, t_near = max(t_near, min(ta, tb)), t_far =
+ *   min(t_far, max(ta, tb)).  A hit iff t_near <= t_far and t_near > 0, at t = t_near (a box behind the origin or containing it never returns).
+ *   Ground: for dz < 0, t = (ground_z - oz)/dz, a candidate iff t > 0.  Winner: the smallest t, the lowest box index on equal t, a box over the ground.
+ * A ray returns iff r_min <= t <= r_max (closed) and it is not dropped.  The draw: one Philox4x32-10 block per ray, counter (r, sweep, (uint32)step,
+ *   0x4C440000 | (step >> 32 & 0xffff)), key seed; word 0: dropped iff uniform24 < p_drop; words 1, 2: nrm = sqrtf(-2 logf(u23)) * cosf(2 pi u23); word 3:
+ *   the intensity uniform24 (csrc/lidar_math.h).  t' = fmaf(sigma_r, nrm, (float)t); point = ((float)(t'*dx), (float)(t'*dy), (float)(t'*dz), intensity),
+ *   each product in fp64, in the SENSOR frame.  p_drop in [0, 1]; sigma_r finite and >= 0; r_min <= r_max; max_pts > 0.
+ * points fp32 [n_sweeps][max_pts][4]: the returns of a sweep in ascending r, the first max_pts kept; n_pts int32 [n_sweeps] = min(returns, max_pts); rows
+ *   from n_pts on are zero.  hit int32 [n_sweeps][max_pts] or NULL: 1 + g for box g, 0 for the ground, -1 from n_pts on.  box_hits int32
+ *   [n_sweeps][box_cap] or NULL: the KEPT returns of box g.
+ * workspace: DEVICE, 8-byte aligned, workspace_bytes >= v2x_lidar_cast_workspace_size (-1 for sizes out of range); it needs no initialisation.
+ * n_sweeps == 0: nothing to do (V2X_OK), whatever the other arguments are.
+ * v2x_lidar_visible_boxes: box g of sweep s is ground truth iff it is valid, its hits are >= min_hits -- box_hits[s][g], or with any_agent != 0
+ *   box_hits[q][g] of any sweep q of the same frame --, its centre in the sensor frame (x, y) = R_s^T (c - o) (fp64, rounded once) has |x| < x_lim and
+ *   |y| < y_lim (compared in fp64), and it does not contain the sensor origin (closed slabs, the cast's lx, ly).  gt_boxes fp32 [n_sweeps][box_cap][5]:
+ *   rows (x, y, w, h, yaw_g - yaw_s), the yaw difference an fp32 subtraction, not wrapped, in ascending box index, rows past gt_count zero; gt_count
+ *   int32 [n_sweeps].  What v2x_det_assign_targets reads. */
+long long v2x_lidar_cast_workspace_size(long long n_sweeps, int n_beams, int n_az, int box_cap);
+int v2x_lidar_cast(const float *sensors, const int32_t *frame_of, long long n_sweeps, const float *boxes, const int32_t *box_count, int n_frames,
+                   int box_cap, const float *beam, int n_beams, const float *az, int n_az, float ground_z, float r_min, float r_max, float sigma_r,
+                   float p_drop, uint64_t seed, uint64_t step, float *points, int32_t *n_pts, int max_pts, int32_t *hit, int32_t *box_hits,
+                   void *workspace, long long workspace_bytes, v2x_stream_t stream);
+int v2x_lidar_visible_boxes(const int32_t *box_hits, const float *sensors, const int32_t *frame_of, long long n_sweeps, const float *boxes,
+                            const int32_t *box_count, int n_frames, int box_cap, int min_hits, int any_agent, float x_lim, float y_lim,
+                            float *gt_boxes, int32_t *gt_count, v2x_stream_t stream);
+
 /* ---------------------------------------------------------------- f-1: the metric (coperception/utils/mean_ap.py::eval_map)
  * Upstream intersects shapely polygons on the host; here the IoU of rotated boxes (x, y, w, h, yaw) is a convex clip in
  * fp64 on the device.

@@ -42,6 +42,10 @@ def build_parser():
     ap.add_argument("--targets", default="radius", choices=["radius", "iou"],
                     help="anchor assignment (DESIGN.md section 3.7): radius = the 0.75 m centre rule, built on the host per item; iou = rotated IoU with "
                          "thresholds and forced best match, one call on the GPU for all items of the step (v2x_det_assign_targets)")
+    ap.add_argument("--scene", default="sampled", choices=["sampled", "raycast"],
+                    help="--data synthetic: sampled = points on every car in range, occluded or not (utils/synthetic_scene.py); raycast = a world of cars "
+                         "and walls swept by every agent's 32-beam LiDAR on the GPU, ground truth = the cars that returned points, IoU targets "
+                         "(v2x_lidar_cast, DESIGN.md section 3.12)")
     ap.add_argument("--loss_type", default="faf_loss", choices=["faf_loss", "corner_loss"],
                     help="localisation term (upstream's config.loss_type; DESIGN.md section 3.10): faf_loss = smooth-L1 on the six box codes; corner_loss = the "
                          "distance between the four corners of the decoded prediction and of the decoded target")
@@ -114,7 +118,7 @@ def main(argv=None):
                                  log=20 if args.log else None, num_workers=args.nworker, opt=opt, sched=sched, targets=args.targets)
         else:
             hist = train_synthetic(model, config, args.steps, args.batch, args.lr, seed=args.seed + epoch,
-                                   log=20 if args.log else None, opt=opt, sched=sched, targets=args.targets)
+                                   log=20 if args.log else None, opt=opt, sched=sched, targets=args.targets, scene=args.scene)
         tail = hist[-20:]
         print("epoch %d (lr %.2e): mean loss of the last %d steps %.4f" % (epoch, opt.param_groups[0]["lr"], len(tail),
                                                                            sum(h[0] for h in tail) / len(tail)))

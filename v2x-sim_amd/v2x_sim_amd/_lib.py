@@ -164,6 +164,12 @@ SIGNATURES = {
     "v2x_seg_rasterize_workspace_size": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int, C.c_int]),
     "v2x_seg_rasterize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "v2x_lidar_cast_workspace_size": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    "v2x_lidar_cast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "v2x_lidar_visible_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "v2x_rotated_iou": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "v2x_match_detections": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),

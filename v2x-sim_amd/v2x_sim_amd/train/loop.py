@@ -47,10 +47,17 @@ def iou_targets_on_device(gt_lists, anchors, device, **assign_kw):
     for m, g in enumerate(gt_lists):
         g = np.asarray(g, np.float32).reshape(-1, 5)
         boxes[m, :g.shape[0]], count[m] = g, g.shape[0]
+    return iou_targets_from_device(torch.from_numpy(boxes).to(device), torch.from_numpy(count).to(device), anchors, device, **assign_kw)
+
+
+def iou_targets_from_device(gt_boxes, gt_count, anchors, device, **assign_kw):
+    """iou_targets_on_device for ground truth that is already on the device in the padded form: gt_boxes (n, cap, 5) fp32, gt_count (n,) int32 (what
+    ops.visible_boxes leaves there) -- no host list, no upload."""
+    import numpy as np
     key = (id(anchors), str(device))
     if key not in _ANCHORS_ON_DEVICE or _ANCHORS_ON_DEVICE[key][0] is not anchors:
         _ANCHORS_ON_DEVICE[key] = (anchors, torch.from_numpy(np.ascontiguousarray(anchors, np.float32)).to(device))
-    res = ops.assign_targets(torch.from_numpy(boxes).to(device), torch.from_numpy(count).to(device), _ANCHORS_ON_DEVICE[key][1], want=(), **assign_kw)
+    res = ops.assign_targets(gt_boxes, gt_count, _ANCHORS_ON_DEVICE[key][1], want=(), **assign_kw)
     return res["labels"], res["reg_targets"], res["reg_loss_mask"].view(torch.bool)
 
 
@@ -66,12 +73,23 @@ def seg_targets_on_device(box_lists, class_lists, config, device, n_classes=8, r
                              n_classes=n_classes, rank=d_rank, want=want, out=out)
 
 
-def synthetic_batch_on_device(config, frames, agents, seed, device, grid=None, anchors=None, with_targets=True, targets="radius", **scene_kw):
+SCENES = ("sampled", "raycast")
+
+
+def synthetic_batch_on_device(config, frames, agents, seed, device, grid=None, anchors=None, with_targets=True, targets="radius", scene="sampled",
+                              **scene_kw):
     """-> data dict in FaFModule.step / predict_all's format (+ 'gt_boxes'[agent][frame] host arrays).
     targets: the assignment rule -- "radius": positives built per item on the host and scattered on the device; "iou": the
-    padded boxes uploaded and assigned by rotated IoU in one call on the device (iou_targets_on_device)."""
+    padded boxes uploaded and assigned by rotated IoU in one call on the device (iou_targets_on_device).
+    scene: "sampled": utils/synthetic_scene.make_scene's points on every car in range; "raycast": a world of boxes swept on the device with occlusion
+    (utils/raycast_scene.raycast_batch_on_device), always with the IoU targets; scene_kw goes to whichever it is."""
     if targets not in TARGET_RULES:
         raise ValueError("targets must be one of %s" % (TARGET_RULES,))
+    if scene not in SCENES:
+        raise ValueError("scene must be one of %s" % (SCENES,))
+    if scene == "raycast":
+        from ..utils import raycast_scene
+        return raycast_scene.raycast_batch_on_device(config, frames, agents, seed, device, grid, anchors, with_targets, **scene_kw)
     anchors = postprocess.build_anchor_map(config) if anchors is None else anchors
     grid = grid or ops.VoxelGrid(config.voxel_size, config.area_extents)
     b = synthetic_scene.make_batch(frames, agents, seed=seed, anchors=anchors if with_targets and targets == "radius" else None, targets="sparse",
@@ -109,10 +127,10 @@ def make_optimizer(model, lr, total_steps):
 
 
 def train_synthetic(model, config, steps, frames_per_step=2, lr=1e-3, seed=0, device="cuda:0", log=None, agents=None,
-                    opt=None, sched=None, targets="radius", **scene_kw):
+                    opt=None, sched=None, targets="radius", scene="sampled", **scene_kw):
     """Adam on freshly generated synthetic scenes (never the same scene twice).  -> list of (loss, cls, loc).
     opt / sched: the run's optimizer and scheduler (make_optimizer); created here for a single self-contained run.
-    targets: "radius" | "iou", see synthetic_batch_on_device."""
+    targets: "radius" | "iou", scene: "sampled" | "raycast", see synthetic_batch_on_device."""
     agents = agents or model.agent_num
     device = torch.device(device)
     model.to(device)
@@ -123,7 +141,7 @@ def train_synthetic(model, config, steps, frames_per_step=2, lr=1e-3, seed=0, de
     hist = []
     for it in range(steps):
         data = synthetic_batch_on_device(config, frames_per_step, agents, seed * 1000003 + it, device, grid, module.anchors,
-                                         targets=targets, **scene_kw)
+                                         targets=targets, scene=scene, **scene_kw)
         hist.append(module.step(data, frames_per_step, agents))
         if sched is not None:
             sched.step()

@@ -28,10 +28,29 @@ def _pose(yaw, x, y):
     return M
 
 
+def warp_transforms(P):
+    """The agents' world poses P (A 4x4 matrices) -> (trans (A, A, 4, 4) f32 in the warp's axis convention, trans_geo (A, A, 4, 4) f32)."""
+    # trans_geo[i, j] = inv(P_i) @ P_j: the geometric transform, agent j's BEV frame -> agent i's (p_i = R p_j + t).
+    # trans[i, j] = the same pose in the axis convention upstream's warp PRESUMES of the dataset's trans_matrices: the
+    # formula shifts the WIDTH axis (BEV y) by 4*T03/128 and the HEIGHT axis (BEV x) by -4*T13/128, which aligns features
+    # iff T03 = -t_y and T13 = t_x (sensor axes rotated 90 degrees against the BEV array axes; the rotation block commutes
+    # and is unchanged).  Verified numerically against the oracle's feature_transformation (tests/test_oracle_cpu.py):
+    # with the plain (t_x, t_y) a warped blob never lands on its cell, with (-t_y, t_x) it always does.
+    agents = len(P)
+    T_geo = np.zeros((agents, agents, 4, 4), np.float32)
+    T = np.zeros((agents, agents, 4, 4), np.float32)
+    for i in range(agents):
+        for j in range(agents):
+            T_geo[i, j] = (np.linalg.inv(P[i]) @ P[j]).astype(np.float32)
+            T[i, j] = T_geo[i, j]
+            T[i, j, 0, 3], T[i, j, 1, 3] = -T_geo[i, j, 1, 3], T_geo[i, j, 0, 3]
+    return T, T_geo
+
+
 def make_scene(agents=5, n_cars=24, seed=0, ground_pts=6000, clutter_pts=1200, pts_per_car=400, max_pts=16384,
                sensor_range=SENSOR_RANGE, gt="own"):
     """-> dict(points (A, max_pts, 4) f32 zero-padded, n_pts (A,) i32, trans (A, A, 4, 4) f32 = the pose of agent j w.r.t.
-    agent i in the warp's axis convention (see the end of this function), trans_geo = inv(P_i) @ P_j, gt_boxes list of
+    agent i in the warp's axis convention (see warp_transforms), trans_geo = inv(P_i) @ P_j, gt_boxes list of
     (G_a, 5) f32 per agent).
     gt='own': an agent's ground truth = the cars inside its BEV extents AND its own sensor range;
     gt='any': ... inside its BEV extents and in range of ANY agent -- cars the ego cannot see itself but a neighbour can
@@ -90,19 +109,7 @@ def make_scene(agents=5, n_cars=24, seed=0, ground_pts=6000, clutter_pts=1200, p
         inside = (np.abs(ctr[:, 0]) < 29.0) & (np.abs(ctr[:, 1]) < 29.0) & seen
         g = np.concatenate([ctr, cars[:, 2:4], (cars[:, 4:5] - yaw_a)], 1)[inside]
         gts.append(g.astype(np.float32))
-    # trans_geo[i, j] = inv(P_i) @ P_j: the geometric transform, agent j's BEV frame -> agent i's (p_i = R p_j + t).
-    # trans[i, j] = the same pose in the axis convention upstream's warp PRESUMES of the dataset's trans_matrices: the
-    # formula shifts the WIDTH axis (BEV y) by 4*T03/128 and the HEIGHT axis (BEV x) by -4*T13/128, which aligns features
-    # iff T03 = -t_y and T13 = t_x (sensor axes rotated 90 degrees against the BEV array axes; the rotation block commutes
-    # and is unchanged).  Verified numerically against the oracle's feature_transformation (tests/test_oracle_cpu.py):
-    # with the plain (t_x, t_y) a warped blob never lands on its cell, with (-t_y, t_x) it always does.
-    T_geo = np.zeros((agents, agents, 4, 4), np.float32)
-    T = np.zeros((agents, agents, 4, 4), np.float32)
-    for i in range(agents):
-        for j in range(agents):
-            T_geo[i, j] = (np.linalg.inv(P[i]) @ P[j]).astype(np.float32)
-            T[i, j] = T_geo[i, j]
-            T[i, j, 0, 3], T[i, j, 1, 3] = -T_geo[i, j, 1, 3], T_geo[i, j, 0, 3]
+    T, T_geo = warp_transforms(P)
     return {"points": points, "n_pts": n_pts, "trans": T, "trans_geo": T_geo, "gt_boxes": gts}
 
 
