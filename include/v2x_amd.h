@@ -721,6 +721,39 @@ int v2x_lidar_cast(const float *sensors, const int32_t *frame_of, long long n_sw
 int v2x_lidar_visible_boxes(const int32_t *box_hits, const float *sensors, const int32_t *frame_of, long long n_sweeps, const float *boxes,
                             const int32_t *box_count, int n_frames, int box_cap, int min_hits, int any_agent, float x_lim, float y_lim,
                             float *gt_boxes, int32_t *gt_count, v2x_stream_t stream);
+/* Moving scenes (DESIGN.md section 3.12 "moving scenes"): the same cast with time.  Every box and every sensor moves in a straight line at constant
+ * velocity with a fixed yaw (no turning, no vertical motion); sensors and boxes give the poses at time 0 in the row formats above, frame_of the sweep's
+ * world -- many sweeps at different times may share one world.  The same contract: two launches (one for the ground truth), no allocation, no host
+ * synchronisation, capturable, every output element written, two calls give identical bytes, n_sweeps == 0 returns V2X_OK before any other check.
+ * box_vel fp32 [n_frames][box_cap][2]: world-frame (vx, vy) of each box; sensor_vel fp32 [n_sweeps][2]: world-frame velocity of each sweep's sensor;
+ *   time_of fp32 [n_sweeps]: the time at which the sweep starts, seconds; az_time fp32 [n_az]: the time offset of each azimuth step within a sweep (the
+ *   host supplies the table, as it supplies every cos / sin pair).
+ * The rule, fp64 from the fp32 inputs, every product and sum rounded on its own: ray r = b * n_az + a of sweep s is cast at T = (double)time_of[s] +
+ *   (double)az_time[a].  For box g: q = (vsx - vgx, vsy - vgy); lx0 = px*cg + py*sg, ly0 = -px*sg + py*cg with p = o0 - c0 as above; dlx = qx*cg + qy*sg,
+ *   dly = -qx*sg + qy*cg; lx = lx0 + dlx*T, ly = ly0 + dly*T.  Everything else is the static rule word for word, evaluated at the ray's own time: w, ux,
+ *   uy, the z slab with lz = oz, the slab test, the ground, the winner and its ties, r_min / r_max, the draw on (seed, step, sweep, ray), the range noise;
+ *   the point is t' * d in the SENSOR frame at the ray's time (a raw sweep: no ego-motion compensation).  A box whose velocity equals the sensor's has
+ *   q = 0 exactly.  With all velocities zero, or all times zero, the outputs are v2x_lidar_cast's bytes.
+ * Not finite: a box with a non-finite velocity is dropped, keeping its index.  A sweep whose time_of or sensor_vel is not finite meets no box and has
+ *   no ground truth (gt_count 0); a ray whose az_time is not finite meets no box.  The ground does not move and still answers both.
+ * workspace: as v2x_lidar_cast's, of v2x_lidar_cast_workspace_size bytes.
+ * v2x_lidar_visible_boxes_moving: the ground truth of sweep s at T_ref = (double)time_of[s] + (double)t_ref (t_ref finite; the tools pass half the sweep
+ *   duration).  Box g is ground truth iff it is valid (finite velocity included), its hits are >= min_hits -- box_hits[s][g], or with any_agent != 0
+ *   box_hits[q][g] of any sweep q of the same world with time_of[q] == time_of[s] (fp32 equality) --, its centre relative to the sensor e = (c0 - o0) +
+ *   (vg - vs) * T_ref, rotated into the sensor frame (x, y) = R_s^T e (fp64, every operation rounded, rounded once to fp32 at the end), has |x| < x_lim
+ *   and |y| < y_lim, and it does not contain the sensor origin at T_ref (closed slabs, the cast's lx, ly at T = T_ref).  gt_boxes, gt_count as
+ *   v2x_lidar_visible_boxes gives them; gt_ids int32 [n_sweeps][box_cap]: the box index of each row -- the car's identity within its world --, -1 past
+ *   gt_count; gt_vel fp32 [n_sweeps][box_cap][2] or NULL: vg - vs rotated into the sensor frame (fp64, rounded once), zero past gt_count.  Rows in
+ *   ascending box index. */
+int v2x_lidar_cast_moving(const float *sensors, const float *sensor_vel, const float *time_of, const int32_t *frame_of, long long n_sweeps,
+                          const float *boxes, const float *box_vel, const int32_t *box_count, int n_frames, int box_cap, const float *beam, int n_beams,
+                          const float *az, const float *az_time, int n_az, float ground_z, float r_min, float r_max, float sigma_r, float p_drop,
+                          uint64_t seed, uint64_t step, float *points, int32_t *n_pts, int max_pts, int32_t *hit, int32_t *box_hits, void *workspace,
+                          long long workspace_bytes, v2x_stream_t stream);
+int v2x_lidar_visible_boxes_moving(const int32_t *box_hits, const float *sensors, const float *sensor_vel, const float *time_of, float t_ref,
+                                   const int32_t *frame_of, long long n_sweeps, const float *boxes, const float *box_vel, const int32_t *box_count,
+                                   int n_frames, int box_cap, int min_hits, int any_agent, float x_lim, float y_lim, float *gt_boxes, int32_t *gt_count,
+                                   int32_t *gt_ids, float *gt_vel, v2x_stream_t stream);
 
 /* ---------------------------------------------------------------- f-1: the metric (coperception/utils/mean_ap.py::eval_map)
  * Upstream intersects shapely polygons on the host; here the IoU of rotated boxes (x, y, w, h, yaw) is a convex clip in

@@ -42,10 +42,11 @@ def build_parser():
     ap.add_argument("--targets", default="radius", choices=["radius", "iou"],
                     help="anchor assignment (DESIGN.md section 3.7): radius = the 0.75 m centre rule, built on the host per item; iou = rotated IoU with "
                          "thresholds and forced best match, one call on the GPU for all items of the step (v2x_det_assign_targets)")
-    ap.add_argument("--scene", default="sampled", choices=["sampled", "raycast"],
+    ap.add_argument("--scene", default="sampled", choices=["sampled", "raycast", "raycast-moving"],
                     help="--data synthetic: sampled = points on every car in range, occluded or not (utils/synthetic_scene.py); raycast = a world of cars "
                          "and walls swept by every agent's 32-beam LiDAR on the GPU, ground truth = the cars that returned points, IoU targets "
-                         "(v2x_lidar_cast, DESIGN.md section 3.12)")
+                         "(v2x_lidar_cast, DESIGN.md section 3.12); raycast-moving = one such world in motion, the items of a step being consecutive "
+                         "sweeps of it (v2x_lidar_cast_moving, utils/raycast_scene.raycast_sequence_on_device)")
     ap.add_argument("--loss_type", default="faf_loss", choices=["faf_loss", "corner_loss"],
                     help="localisation term (upstream's config.loss_type; DESIGN.md section 3.10): faf_loss = smooth-L1 on the six box codes; corner_loss = the "
                          "distance between the four corners of the decoded prediction and of the decoded target")

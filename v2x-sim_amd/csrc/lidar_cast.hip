@@ -369,3 +369,274 @@ extern "C" int v2x_lidar_visible_boxes(const int32_t *box_hits, const float *sen
                                   gt_count};
     return v2x_launch<lidar_visible_kernel, 0>("lidar_visible_kernel", dim3((unsigned)n_sweeps), dim3(256), 0, (hipStream_t)stream, p);
 }
+
+// ---- moving scenes (DESIGN.md section 3.12 "moving scenes") ---------------------------------------------------------------------------------------
+// Every box and every sensor moves in a straight line at constant velocity with a fixed yaw; sensors / boxes give the poses at time 0.  A sweep takes
+// time: ray r = b * NA + a of sweep s is cast at T = (double)time_of[s] + (double)az_time[a] (lidar_math.h), against the boxes where they are THEN.
+//   THE RULE.  For box g with q = (vsx - vgx, vsy - vgy) (sensor minus box, fp64 from the fp32 velocities): lx0 = px*cg + py*sg, ly0 = -px*sg + py*cg
+//   with p = o0 - c0 exactly as the static rule has them; dlx = qx*cg + qy*sg, dly = -qx*sg + qy*cg; lx = lx0 + dlx*T, ly = ly0 + dly*T, every product
+//   and sum rounded on its own.  Everything else is the static rule at the ray's own time: w, ux, uy, the z slab with lz = oz (no vertical motion),
+//   the ground, the winner and its ties, r_min / r_max, the draw on (seed, step, sweep, ray), the point t' * d in the SENSOR frame at the ray's time
+//   (a raw sweep: no ego-motion compensation).  A box whose velocity equals the sensor's has q = 0 exactly and is met as if both stood still.
+//   A box with a non-finite velocity is dropped, keeping its index.  A sweep whose time_of or sensor_vel is not finite meets no box and has no ground
+//   truth; a ray whose az_time is not finite meets no box; the ground, which does not move, still answers both.
+//   lidar_cast_moving_kernel     lidar_cast_kernel's grid, box load, ballot and prefix; an LDS row carries dlx, dly after the static eight.  It writes
+//                                the same per-ray record and per-chunk counts, so lidar_compact_kernel follows it unchanged.
+//   lidar_visible_moving_kernel  one workgroup per sweep, thread g = box g, at T_ref = (double)time_of[s] + (double)t_ref.
+struct lidar_moving_args {
+    lidar_args base;
+    const float *box_vel;        // [F][cap][2]
+    const float *sensor_vel;     // [n][2]
+    const float *time_of;        // [n]
+    const float *az_time;        // [NA]
+};
+
+__global__ __launch_bounds__(256) void lidar_cast_moving_kernel(lidar_moving_args m) {
+    __shared__ double s_box[LIDAR_MAX_BOX][10];       // lx0, ly0, cg, sg, w/2, h/2, z0, z1, dlx, dly
+    __shared__ int s_index[LIDAR_MAX_BOX];
+    __shared__ int s_wave_n[4], s_wave_ret[4];
+
+    const lidar_args &p = m.base;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int s = blockIdx.x / p.n_chunks, chunk = blockIdx.x - s * p.n_chunks;
+    const float *sen = p.sensors + (size_t)s * 6;
+    const double ox = (double)sen[0], oy = (double)sen[1], oz = (double)sen[2], cs = (double)sen[4], sn = (double)sen[5];
+    const float vsx = m.sensor_vel[(size_t)s * 2], vsy = m.sensor_vel[(size_t)s * 2 + 1], t0 = m.time_of[s];
+    const bool sweep_ok = lidar_finite(vsx) && lidar_finite(vsy) && lidar_finite(t0);
+    const int f = p.frame_of[s];
+    const int count = lidar_count(p.box_count, p.n_frames, p.cap, f);
+
+    if (chunk == 0 && p.box_hits && tid < p.cap) p.box_hits[(size_t)s * p.cap + tid] = 0;     // the compaction launch adds to it
+
+    bool live = false;
+    float b[9], vgx = 0.0f, vgy = 0.0f;
+    if (tid < count) {
+        const float *src = p.boxes + ((size_t)f * p.cap + tid) * 9;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) b[e] = src[e];
+        vgx = m.box_vel[((size_t)f * p.cap + tid) * 2];
+        vgy = m.box_vel[((size_t)f * p.cap + tid) * 2 + 1];
+        live = sweep_ok && lidar_box_valid(b) && lidar_finite(vgx) && lidar_finite(vgy);
+    }
+    const unsigned long long mask = __ballot(live);
+    if (lane == 0) s_wave_n[wave] = __popcll(mask);
+    __syncthreads();
+    int base = 0, n_live = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) base += s_wave_n[w];
+        n_live += s_wave_n[w];
+    }
+    if (live) {
+        const int k = base + __popcll(mask & ((1ull << lane) - 1ull));
+        const double px = ox - (double)b[0], py = oy - (double)b[1], cg = (double)b[5], sg = (double)b[6];
+        const double qx = (double)vsx - (double)vgx, qy = (double)vsy - (double)vgy;
+        s_box[k][0] = px * cg + py * sg;
+        s_box[k][1] = -px * sg + py * cg;
+        s_box[k][2] = cg;
+        s_box[k][3] = sg;
+        s_box[k][4] = (double)b[2] / 2.0;
+        s_box[k][5] = (double)b[3] / 2.0;
+        s_box[k][6] = (double)b[7];
+        s_box[k][7] = (double)b[8];
+        s_box[k][8] = qx * cg + qy * sg;
+        s_box[k][9] = -qx * sg + qy * cg;
+        s_index[k] = tid;
+    }
+    __syncthreads();
+
+    const int r = chunk * LIDAR_CHUNK + tid;
+    bool ret = false;
+    int id = -1;
+    float t_rep = 0.0f;
+    if (r < p.n_rays) {
+        double dx, dy, dz;
+        lidar_direction(p, r, dx, dy, dz);
+        const float ta = m.az_time[r % p.n_az];
+        const double T = lidar_ray_time(t0, ta);
+        const int n_box = lidar_finite(ta) ? n_live : 0;      // a ray without a time meets the ground alone
+        const double wx = cs * dx - sn * dy, wy = sn * dx + cs * dy;
+        double best = __builtin_inf();
+        for (int k = 0; k < n_box; ++k) {                     // LDS broadcast reads, ascending box index
+            const double cg = s_box[k][2], sg = s_box[k][3], hw = s_box[k][4], hh = s_box[k][5];
+            const double ux = wx * cg + wy * sg, uy = -wx * sg + wy * cg;
+            const double lx = lidar_moved(s_box[k][0], s_box[k][8], T), ly = lidar_moved(s_box[k][1], s_box[k][9], T);
+            double t_near = -__builtin_inf(), t_far = __builtin_inf();
+            if (!lidar_slab(lx, ux, -hw, hw, t_near, t_far)) continue;
+            if (!lidar_slab(ly, uy, -hh, hh, t_near, t_far)) continue;
+            if (!(t_near <= t_far)) continue;                 // the z slab can only narrow the interval
+            if (!lidar_slab(oz, dz, s_box[k][6], s_box[k][7], t_near, t_far)) continue;
+            if (t_near <= t_far && t_near > 0.0 && t_near < best) {
+                best = t_near;
+                id = 1 + s_index[k];
+            }
+        }
+        if (dz < 0.0) {
+            const double t = ((double)p.ground_z - oz) / dz;
+            if (t > 0.0 && t < best) {                        // strictly: a box at the same t keeps the ray
+                best = t;
+                id = 0;
+            }
+        }
+        if (id >= 0 && best >= (double)p.r_min && best <= (double)p.r_max) {
+            const ChanWords d = lidar_words(p.seed, p.step, (uint32_t)s, (uint32_t)r);
+            if (!lidar_dropped(d, p.p_drop)) {
+                ret = true;
+                t_rep = lidar_noisy_range(best, p.sigma_r, p.sigma_r != 0.0f ? lidar_normal(d) : 0.0f);
+            }
+        }
+        p.rec[(size_t)s * p.n_rays + r] = make_uint2(__float_as_uint(t_rep), (uint32_t)(ret ? id : -1));
+    }
+    const unsigned long long rmask = __ballot(ret);
+    if (lane == 0) s_wave_ret[wave] = __popcll(rmask);
+    __syncthreads();
+    if (tid == 0) p.chunk_n[blockIdx.x] = s_wave_ret[0] + s_wave_ret[1] + s_wave_ret[2] + s_wave_ret[3];
+}
+
+struct lidar_visible_moving_args {
+    lidar_visible_args base;
+    const float *box_vel;        // [F][cap][2]
+    const float *sensor_vel;     // [n][2]
+    const float *time_of;        // [n]
+    float t_ref;
+    int32_t *gt_ids;             // [n][cap]
+    float *gt_vel;               // [n][cap][2] or null
+};
+
+__global__ __launch_bounds__(256) void lidar_visible_moving_kernel(lidar_visible_moving_args m) {
+    __shared__ int s_wave_n[4];
+    const lidar_visible_args &p = m.base;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, s = blockIdx.x;
+    const float *sen = p.sensors + (size_t)s * 6;
+    const float vsx = m.sensor_vel[(size_t)s * 2], vsy = m.sensor_vel[(size_t)s * 2 + 1], t0 = m.time_of[s];
+    const bool sweep_ok = lidar_finite(vsx) && lidar_finite(vsy) && lidar_finite(t0);
+    const int f = p.frame_of[s];
+    const int count = lidar_count(p.box_count, p.n_frames, p.cap, f);
+
+    bool keep = false;
+    float row[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, vel[2] = {0.0f, 0.0f};
+    if (tid < count && sweep_ok) {
+        float b[9];
+        const float *src = p.boxes + ((size_t)f * p.cap + tid) * 9;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) b[e] = src[e];
+        const float vgx = m.box_vel[((size_t)f * p.cap + tid) * 2], vgy = m.box_vel[((size_t)f * p.cap + tid) * 2 + 1];
+        int hits = p.box_hits[(size_t)s * p.cap + tid];
+        if (p.any_agent)                                      // the sweeps of the same world AT THE SAME TIME (fp32 equality of time_of)
+            for (int q = 0; q < p.n_sweeps; ++q)
+                if (p.frame_of[q] == f && m.time_of[q] == t0) hits = max(hits, p.box_hits[(size_t)q * p.cap + tid]);
+        if (lidar_box_valid(b) && lidar_finite(vgx) && lidar_finite(vgy) && hits >= p.min_hits) {
+            const double ox = (double)sen[0], oy = (double)sen[1], oz = (double)sen[2], cs = (double)sen[4], sn = (double)sen[5];
+            const double T = lidar_ray_time(t0, m.t_ref);
+            const double ex = lidar_rel_centre((double)b[0], ox, (double)vgx, (double)vsx, T);
+            const double ey = lidar_rel_centre((double)b[1], oy, (double)vgy, (double)vsy, T);
+            const double x = ex * cs + ey * sn, y = -ex * sn + ey * cs;                      // R_s^T (c - o) at T_ref
+            const double px = ox - (double)b[0], py = oy - (double)b[1], cg = (double)b[5], sg = (double)b[6];
+            const double qx = (double)vsx - (double)vgx, qy = (double)vsy - (double)vgy;
+            const double lx = lidar_moved(px * cg + py * sg, qx * cg + qy * sg, T), ly = lidar_moved(-px * sg + py * cg, -qx * sg + qy * cg, T);
+            const bool inside = fabs(lx) <= (double)b[2] / 2.0 && fabs(ly) <= (double)b[3] / 2.0 && oz >= (double)b[7] && oz <= (double)b[8];
+            if (fabs(x) < (double)p.x_lim && fabs(y) < (double)p.y_lim && !inside) {
+                const double rvx = (double)vgx - (double)vsx, rvy = (double)vgy - (double)vsy;
+                keep = true;
+                row[0] = (float)x;
+                row[1] = (float)y;
+                row[2] = b[2];
+                row[3] = b[3];
+                row[4] = b[4] - sen[3];
+                vel[0] = (float)(rvx * cs + rvy * sn);
+                vel[1] = (float)(-rvx * sn + rvy * cs);
+            }
+        }
+    }
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) s_wave_n[wave] = __popcll(mask);
+    __syncthreads();
+    int base = 0, n_keep = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) base += s_wave_n[w];
+        n_keep += s_wave_n[w];
+    }
+    float *out = p.gt_boxes + (size_t)s * p.cap * 5;
+    int32_t *ids = m.gt_ids + (size_t)s * p.cap;
+    float *ov = m.gt_vel ? m.gt_vel + (size_t)s * p.cap * 2 : nullptr;
+    if (keep) {                                               // k <= tid < cap
+        const int k = base + __popcll(mask & ((1ull << lane) - 1ull));
+#pragma unroll
+        for (int e = 0; e < 5; ++e) out[k * 5 + e] = row[e];
+        ids[k] = tid;
+        if (ov) {
+            ov[k * 2] = vel[0];
+            ov[k * 2 + 1] = vel[1];
+        }
+    }
+    if (tid >= n_keep && tid < p.cap) {
+#pragma unroll
+        for (int e = 0; e < 5; ++e) out[tid * 5 + e] = 0.0f;
+        ids[tid] = -1;
+        if (ov) {
+            ov[tid * 2] = 0.0f;
+            ov[tid * 2 + 1] = 0.0f;
+        }
+    }
+    if (tid == 0) p.gt_count[s] = n_keep;
+}
+
+extern "C" int v2x_lidar_cast_moving(const float *sensors, const float *sensor_vel, const float *time_of, const int32_t *frame_of, long long n_sweeps,
+                                     const float *boxes, const float *box_vel, const int32_t *box_count, int n_frames, int box_cap, const float *beam,
+                                     int n_beams, const float *az, const float *az_time, int n_az, float ground_z, float r_min, float r_max, float sigma_r,
+                                     float p_drop, uint64_t seed, uint64_t step, float *points, int32_t *n_pts, int max_pts, int32_t *hit,
+                                     int32_t *box_hits, void *workspace, long long workspace_bytes, v2x_stream_t stream) {
+    if (n_sweeps == 0) return V2X_OK;
+    V2X_REQUIRE(n_sweeps > 0, "v2x_lidar_cast_moving: negative n_sweeps (%lld)", n_sweeps);
+    V2X_REQUIRE(box_cap >= 1 && box_cap <= LIDAR_MAX_BOX, "v2x_lidar_cast_moving: box_cap=%d must lie in [1, %d]", box_cap, LIDAR_MAX_BOX);
+    V2X_REQUIRE(n_frames >= 1, "v2x_lidar_cast_moving: n_frames=%d must be >= 1", n_frames);
+    V2X_REQUIRE(max_pts > 0, "v2x_lidar_cast_moving: max_pts=%d must be > 0", max_pts);
+    V2X_REQUIRE(lidar_shape_ok(n_sweeps, n_beams, n_az, box_cap),
+                "v2x_lidar_cast_moving: n_sweeps=%lld, n_beams=%d, n_az=%d: sizes must be >= 1, n_beams*n_az <= 2^24 and n_sweeps*chunks < 2^31", n_sweeps,
+                n_beams, n_az);
+    V2X_REQUIRE(p_drop >= 0.0f && p_drop <= 1.0f, "v2x_lidar_cast_moving: p_drop=%g must lie in [0, 1]", (double)p_drop);
+    V2X_REQUIRE(sigma_r >= 0.0f && sigma_r <= 3.0e38f, "v2x_lidar_cast_moving: sigma_r=%g must be finite and >= 0", (double)sigma_r);
+    V2X_REQUIRE(r_min <= r_max, "v2x_lidar_cast_moving: r_min (%g) <= r_max (%g) needed", (double)r_min, (double)r_max);
+    V2X_REQUIRE(ground_z >= -3.0e38f && ground_z <= 3.0e38f, "v2x_lidar_cast_moving: ground_z=%g must be finite", (double)ground_z);
+    V2X_REQUIRE(sensors && sensor_vel && time_of && frame_of && boxes && box_vel && box_count && beam && az && az_time && points && n_pts,
+                "v2x_lidar_cast_moving: null pointer (only hit and box_hits may be null)");
+    const long long need = v2x_lidar_cast_workspace_size(n_sweeps, n_beams, n_az, box_cap);
+    V2X_REQUIRE(workspace && workspace_bytes >= need, "v2x_lidar_cast_moving: workspace of %lld bytes, %lld needed", workspace ? workspace_bytes : 0LL, need);
+    V2X_REQUIRE(lidar_aligned(workspace, 8), "v2x_lidar_cast_moving: workspace must be 8-byte aligned");
+    V2X_REQUIRE(lidar_aligned(sensors, 4) && lidar_aligned(sensor_vel, 4) && lidar_aligned(time_of, 4) && lidar_aligned(frame_of, 4) && lidar_aligned(boxes, 4) &&
+                    lidar_aligned(box_vel, 4) && lidar_aligned(box_count, 4) && lidar_aligned(beam, 4) && lidar_aligned(az, 4) && lidar_aligned(az_time, 4) &&
+                    lidar_aligned(points, 4) && lidar_aligned(n_pts, 4) && lidar_aligned(hit, 4) && lidar_aligned(box_hits, 4),
+                "v2x_lidar_cast_moving: int32 / fp32 arrays must be 4-byte aligned");
+    const int n_rays = n_beams * n_az, n_chunks = (int)lidar_chunks(n_rays);
+    uint2 *rec = static_cast<uint2 *>(workspace);
+    const lidar_moving_args m = {{sensors, frame_of, boxes, box_count, n_frames, box_cap, beam, az, n_az, n_rays, n_chunks, ground_z, r_min, r_max, sigma_r,
+                                  p_drop, seed, step, points, n_pts, max_pts, hit, box_hits, rec, reinterpret_cast<int32_t *>(rec + (size_t)n_sweeps * n_rays)},
+                                 box_vel, sensor_vel, time_of, az_time};
+    const dim3 grid((unsigned)(n_sweeps * n_chunks));
+    const int rc = v2x_launch<lidar_cast_moving_kernel, 0>("lidar_cast_moving_kernel", grid, dim3(256), 0, (hipStream_t)stream, m);
+    if (rc != V2X_OK) return rc;
+    return v2x_launch<lidar_compact_kernel, 0>("lidar_compact_kernel", grid, dim3(256), 0, (hipStream_t)stream, m.base);
+}
+
+extern "C" int v2x_lidar_visible_boxes_moving(const int32_t *box_hits, const float *sensors, const float *sensor_vel, const float *time_of, float t_ref,
+                                              const int32_t *frame_of, long long n_sweeps, const float *boxes, const float *box_vel, const int32_t *box_count,
+                                              int n_frames, int box_cap, int min_hits, int any_agent, float x_lim, float y_lim, float *gt_boxes,
+                                              int32_t *gt_count, int32_t *gt_ids, float *gt_vel, v2x_stream_t stream) {
+    if (n_sweeps == 0) return V2X_OK;
+    V2X_REQUIRE(n_sweeps > 0 && n_sweeps <= 0x7fffffffLL, "v2x_lidar_visible_boxes_moving: n_sweeps=%lld must lie in [0, 2^31)", n_sweeps);
+    V2X_REQUIRE(box_cap >= 1 && box_cap <= LIDAR_MAX_BOX, "v2x_lidar_visible_boxes_moving: box_cap=%d must lie in [1, %d]", box_cap, LIDAR_MAX_BOX);
+    V2X_REQUIRE(n_frames >= 1, "v2x_lidar_visible_boxes_moving: n_frames=%d must be >= 1", n_frames);
+    V2X_REQUIRE(x_lim > 0.0f && y_lim > 0.0f, "v2x_lidar_visible_boxes_moving: x_lim (%g) and y_lim (%g) must be > 0", (double)x_lim, (double)y_lim);
+    V2X_REQUIRE(t_ref >= -3.0e38f && t_ref <= 3.0e38f, "v2x_lidar_visible_boxes_moving: t_ref=%g must be finite", (double)t_ref);
+    V2X_REQUIRE(box_hits && sensors && sensor_vel && time_of && frame_of && boxes && box_vel && box_count && gt_boxes && gt_count && gt_ids,
+                "v2x_lidar_visible_boxes_moving: null pointer (only gt_vel may be null)");
+    V2X_REQUIRE(lidar_aligned(box_hits, 4) && lidar_aligned(sensors, 4) && lidar_aligned(sensor_vel, 4) && lidar_aligned(time_of, 4) && lidar_aligned(frame_of, 4) &&
+                    lidar_aligned(boxes, 4) && lidar_aligned(box_vel, 4) && lidar_aligned(box_count, 4) && lidar_aligned(gt_boxes, 4) &&
+                    lidar_aligned(gt_count, 4) && lidar_aligned(gt_ids, 4) && lidar_aligned(gt_vel, 4),
+                "v2x_lidar_visible_boxes_moving: int32 / fp32 arrays must be 4-byte aligned");
+    const lidar_visible_moving_args m = {{box_hits, sensors, frame_of, (int)n_sweeps, boxes, box_count, n_frames, box_cap, min_hits, any_agent, x_lim, y_lim,
+                                          gt_boxes, gt_count},
+                                         box_vel, sensor_vel, time_of, t_ref, gt_ids, gt_vel};
+    return v2x_launch<lidar_visible_moving_kernel, 0>("lidar_visible_moving_kernel", dim3((unsigned)n_sweeps), dim3(256), 0, (hipStream_t)stream, m);
+}

@@ -73,7 +73,7 @@ def seg_targets_on_device(box_lists, class_lists, config, device, n_classes=8, r
                              n_classes=n_classes, rank=d_rank, want=want, out=out)
 
 
-SCENES = ("sampled", "raycast")
+SCENES = ("sampled", "raycast", "raycast-moving")
 
 
 def synthetic_batch_on_device(config, frames, agents, seed, device, grid=None, anchors=None, with_targets=True, targets="radius", scene="sampled",
@@ -82,7 +82,9 @@ def synthetic_batch_on_device(config, frames, agents, seed, device, grid=None, a
     targets: the assignment rule -- "radius": positives built per item on the host and scattered on the device; "iou": the
     padded boxes uploaded and assigned by rotated IoU in one call on the device (iou_targets_on_device).
     scene: "sampled": utils/synthetic_scene.make_scene's points on every car in range; "raycast": a world of boxes swept on the device with occlusion
-    (utils/raycast_scene.raycast_batch_on_device), always with the IoU targets; scene_kw goes to whichever it is."""
+    (utils/raycast_scene.raycast_batch_on_device), always with the IoU targets; "raycast-moving": ONE such world in motion,
+    the `frames` items being consecutive steps of it (utils/raycast_scene.raycast_sequence_on_device; make_moving_world's keywords and the sequence's
+    are both taken from scene_kw); scene_kw goes to whichever it is."""
     if targets not in TARGET_RULES:
         raise ValueError("targets must be one of %s" % (TARGET_RULES,))
     if scene not in SCENES:
@@ -90,6 +92,12 @@ def synthetic_batch_on_device(config, frames, agents, seed, device, grid=None, a
     if scene == "raycast":
         from ..utils import raycast_scene
         return raycast_scene.raycast_batch_on_device(config, frames, agents, seed, device, grid, anchors, with_targets, **scene_kw)
+    if scene == "raycast-moving":
+        from ..utils import raycast_scene
+        world_kw = {k: scene_kw.pop(k) for k in ("n_cars", "n_walls", "p_parked", "speed", "extent", "agent_extent") if k in scene_kw}
+        world = scene_kw.pop("world", None) or raycast_scene.make_moving_world(1, agents, seed, **world_kw)
+        return raycast_scene.raycast_sequence_on_device(config, world, frames, device=device, grid=grid, anchors=anchors, with_targets=with_targets,
+                                                        seed=seed, **scene_kw)
     anchors = postprocess.build_anchor_map(config) if anchors is None else anchors
     grid = grid or ops.VoxelGrid(config.voxel_size, config.area_extents)
     b = synthetic_scene.make_batch(frames, agents, seed=seed, anchors=anchors if with_targets and targets == "radius" else None, targets="sparse",
@@ -130,7 +138,7 @@ def train_synthetic(model, config, steps, frames_per_step=2, lr=1e-3, seed=0, de
                     opt=None, sched=None, targets="radius", scene="sampled", **scene_kw):
     """Adam on freshly generated synthetic scenes (never the same scene twice).  -> list of (loss, cls, loc).
     opt / sched: the run's optimizer and scheduler (make_optimizer); created here for a single self-contained run.
-    targets: "radius" | "iou", scene: "sampled" | "raycast", see synthetic_batch_on_device."""
+    targets: "radius" | "iou", scene: "sampled" | "raycast" | "raycast-moving", see synthetic_batch_on_device."""
     agents = agents or model.agent_num
     device = torch.device(device)
     model.to(device)
