@@ -597,7 +597,9 @@ int v2x_zero_insert_bf16(const uint16_t *dy, int N, int Ho, int Wo, int C, uint1
  * out_boxes fp32 [n][cap][5], out_scores fp32 [n][cap], out_index int32 [n][cap] (anchor index of each detection),
  * out_count int32 [n]: number of detections of map i, or -(number of candidates) when more than `cap` anchors passed the
  * threshold (nothing else is written for that map: the caller retries with a higher threshold or post-processes on the host).
- * key_scratch: uint64 [n][cap], count_scratch: int32 [n] (caller-owned workspace). */
+ * Entries >= out_count of out_scores and out_index are not written; rows >= out_count of out_boxes are the call's staging area (the decoded
+ * candidates, kept ones compacted to the front afterwards): their contents are unspecified.  The caller clears nothing.
+ * key_scratch: uint64 [n][cap], count_scratch: int32 [n] (caller-owned workspace; cleared and written by the call). */
 int v2x_det_postprocess(const float *cls, const float *loc, const float *anchors, int n, int M, float score_thr,
                         float nms_thr, int cap, float *out_boxes, float *out_scores, int32_t *out_index,
                         int32_t *out_count, unsigned long long *key_scratch, int32_t *count_scratch,
@@ -633,7 +635,8 @@ int v2x_det_nms_candidates(const unsigned long long *keys, const float *codes, c
  * ascending agent index, then by ascending rank in the source list.  Suppression: exactly v2x_det_postprocess's (rotated != 0: _rotated's).
  * out_boxes fp32 [A*B][cap_out][5], out_scores fp32 [A*B][cap_out] (the source's bits), out_src int32 [A*B][cap_out] = j*cap_in + rank of the
  * source, out_count int32 [A*B]; negative = not computed: -(merged candidates) when they exceed cap_out, -(cap_out + 1) when the ego or a
- * linked source carried a negative count itself.  cap_in, cap_out: powers of two in [64, 4096].  A*B == 0: nothing to do (V2X_OK). */
+ * linked source carried a negative count itself.  cap_in, cap_out: powers of two in [64, 4096].  A*B == 0: nothing to do (V2X_OK).
+ * Entries >= out_count of out_scores and out_src are not written; rows >= out_count of out_boxes are staging area, contents unspecified. */
 int v2x_det_late_fuse(const float *boxes, const float *scores, const int32_t *counts, int A, int B, int cap_in,
                       const float *rigid, const uint8_t *link, float x_lo, float x_hi, float y_lo, float y_hi,
                       float nms_thr, int rotated, int cap_out, float *out_boxes, float *out_scores,

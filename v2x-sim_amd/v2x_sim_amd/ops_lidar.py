@@ -85,7 +85,7 @@ def lidar_cast(sensors, frame_of, boxes, box_count, beam, az, max_pts, ground_z=
     nbytes = lib.v2x_lidar_cast_workspace_size(n, int(beam.shape[0]), int(az.shape[0]), cap)
     if nbytes < 0:
         raise ValueError("lidar_cast: sizes out of range (n=%d, beams=%d, azimuths=%d, cap=%d in [1, 256])" % (n, beam.shape[0], az.shape[0], cap))
-    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=dev)
+    ws = torch.empty(((max(nbytes, 8) + 7) // 8,), dtype=torch.int64, device=dev)     # rounded UP: the size is a multiple of 4, not of 8 (an odd n * chunks)
     _lib.check(lib.v2x_lidar_cast(_dev(sensors, torch.float32, "sensors") if n else None, _dev(frame_of, torch.int32, "frame_of") if n else None, n,
                                   _dev(boxes, torch.float32, "boxes"), _dev(box_count, torch.int32, "box_count"), F, cap, _dev(beam, torch.float32, "beam"),
                                   int(beam.shape[0]), _dev(az, torch.float32, "az"), int(az.shape[0]), C.c_float(ground_z), C.c_float(r_min), C.c_float(r_max),
@@ -157,7 +157,7 @@ def lidar_cast_moving(sensors, sensor_vel, time_of, frame_of, boxes, box_vel, bo
     nbytes = lib.v2x_lidar_cast_workspace_size(n, int(beam.shape[0]), int(az.shape[0]), cap)
     if nbytes < 0:
         raise ValueError("lidar_cast_moving: sizes out of range (n=%d, beams=%d, azimuths=%d, cap=%d in [1, 256])" % (n, beam.shape[0], az.shape[0], cap))
-    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=dev)
+    ws = torch.empty(((max(nbytes, 8) + 7) // 8,), dtype=torch.int64, device=dev)     # rounded UP: the size is a multiple of 4, not of 8 (an odd n * chunks)
     _lib.check(lib.v2x_lidar_cast_moving(
         _dev(sensors, torch.float32, "sensors") if n else None, _dev(sensor_vel, torch.float32, "sensor_vel") if n else None,
         _dev(time_of, torch.float32, "time_of") if n else None, _dev(frame_of, torch.int32, "frame_of") if n else None, n,
