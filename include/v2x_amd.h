@@ -758,6 +758,38 @@ int v2x_lidar_visible_boxes_moving(const int32_t *box_hits, const float *sensors
                                    int n_frames, int box_cap, int min_hits, int any_agent, float x_lim, float y_lim, float *gt_boxes, int32_t *gt_count,
                                    int32_t *gt_ids, float *gt_vel, v2x_stream_t stream);
 
+/* ---------------------------------------------------------------- f-2: visibility maps (upstream's data preparation: `vis_maps`, Config.use_vis)
+ * The voxeliser keeps where a sweep's returns end; these entries keep the space each beam crossed before it returned.  The rule -- DESIGN.md section
+ * 3.13 -- in short: jobs as in v2x_voxelize_fused_bits (job j moves cloud src_cloud[j] by xform[j], fp32 ((x*m0 + y*m1) + z*m2) + m3 with every
+ * operation rounded, and writes into grid dst_grid[j]; several jobs may share a target; a job naming a cloud or grid that does not exist is skipped),
+ * plus a ray origin origin[j] (device fp32 [n_jobs][3], in the cloud's frame) moved by the same arithmetic.  origin == NULL: the zero vector (a ray-cast
+ * sweep; the moved origin is then the translation column); xform == NULL: identity; src_cloud == dst_grid == NULL (both or neither): job j = cloud j ->
+ * grid j.  A moved coordinate c of axis k becomes q = quot(c) - floor(lo_k / voxel_k) in fp64, quot = a1's (the exact reciprocal's product for a
+ * power-of-two voxel size, else the division): voxel faces are the integers, the grid is the box [0,X] x [0,Y] x [0,Z].  The segment q_o -> q_p is
+ * clipped to the box and walked row by row in x and column by column in y; in each column the ray's z at entry and at exit give a contiguous range of
+ * z bits: one OR.  Every crossing parameter is computed from its lattice index, (i - q_o) / d, never accumulated; every fp64 operation is rounded on its
+ * own.  Voxels are closed: a ray touching a face, edge or corner sets the voxels on both sides.  A ray is skipped when its index is >= min(n_pts,
+ * max_pts), when a moved coordinate is not finite, when it has zero length or when it never meets the box.  An origin outside the grid is legal (the
+ * clipped part is walked); an endpoint outside carves to the exit.  The endpoint's own voxel gets no special treatment: occupied is a1's result
+ * (v2x_voxelize_bits / v2x_voxelize_fused_bits on the same clouds and jobs), free is trav & ~occ, unknown is neither.  A return in the sliver between
+ * the index lattice and a1's open extents is not occupied, so its voxel may read as free.
+ * trav_bits: [n_grids][X][Y] uint32, bit z = some ray passed through voxel (x, y, z); cleared by the call, every word written; Z <= 32, n_jobs <= 65535.
+ * No allocation, no host synchronisation, capturable; OR is idempotent: the bytes do not depend on the order, two calls give the same.  Two kernel
+ * forms, bit-identical, chosen by the grid's shape alone: Z <= 16 with X * Y 16-bit pixels within 128 KiB and X * Y % 8 == 0 (and a 16-byte aligned
+ * trav_bits) keeps the grid in LDS, cut into bands of 16 rows, one workgroup per grid and band; any other shape ORs into the cleared grid with
+ * device-scope atomics. */
+int v2x_lidar_freespace_bits(const float *pts, const int32_t *n_pts, int n_clouds, int max_pts, int pt_stride, const float *origin, const float *xform,
+                             const int32_t *src_cloud, const int32_t *dst_grid, int n_jobs, int n_grids, const double *extents, const double *voxel,
+                             const int32_t *dims_xyz, uint32_t *trav_bits, v2x_stream_t stream);
+/* occ / trav bits -> upstream's vis_maps layout [n][X][Y][Z] fp32: v_occ where occupied, v_free where trav & ~occ, else v_unknown.  Every element is written. */
+int v2x_vis_bits_to_dense_f32(const uint32_t *occ_bits, const uint32_t *trav_bits, int n, int X, int Y, int Z, float v_occ, float v_free, float v_unknown,
+                              float *out, v2x_stream_t stream);
+/* Segmentation labels (uint8 [n][X][Y], v2x_seg_rasterize's) with the cells nobody observed set to the ignore class: labels_out[m][x][y] = ignore where
+ * ((occ | trav) & z_mask) == 0, else labels_in.  ignore in [0, 255].  In place (labels_out == labels_in) is allowed: an element is read and written by
+ * one thread only. */
+int v2x_vis_mask_labels(const uint8_t *labels_in, const uint32_t *occ_bits, const uint32_t *trav_bits, int n, int X, int Y, uint32_t z_mask, int ignore,
+                        uint8_t *labels_out, v2x_stream_t stream);
+
 /* ---------------------------------------------------------------- f-1: the metric (coperception/utils/mean_ap.py::eval_map)
  * Upstream intersects shapely polygons on the host; here the IoU of rotated boxes (x, y, w, h, yaw) is a convex clip in
  * fp64 on the device.

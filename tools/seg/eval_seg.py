@@ -38,6 +38,9 @@ def build_parser():
     ap.add_argument("--batch", default=2, type=int)
     ap.add_argument("--seed", default=4242, type=int)
     ap.add_argument("--rsu", default=1, type=int, help="parsed dataset: 1 = agent0 (the RSU) takes part, 0 = vehicles only")
+    ap.add_argument("--scene", default="sampled", choices=["sampled", "raycast"],
+                    help="synthetic data: raycast = tools/seg/train_seg.py's ray-cast world (any --com is then evaluated by this file's loop)")
+    ap.add_argument("--observed", default="own", choices=["own", "any", "all"], help="--scene raycast: which cells count as observed (the others are ignored)")
     return ap
 
 
@@ -77,8 +80,8 @@ def evaluate(argv):
         batches = ([dataset[i] for i in range(s0, min(s0 + args.batch, len(dataset)))] for s0 in range(0, len(dataset), args.batch))
         batches = ((seg_batch_on_device(smp, grid, device), len(smp)) for smp in batches)
     else:
-        batches = ((seg_batch(config, min(args.batch, args.frames - s0), A, args.seed + s0, device, grid),
-                    min(args.batch, args.frames - s0)) for s0 in range(0, args.frames, args.batch))
+        batches = ((seg_batch(config, min(args.batch, args.frames - s0), A, args.seed + s0, device, grid, n_classes=model.n_classes, scene=args.scene,
+                              observed=args.observed), min(args.batch, args.frames - s0)) for s0 in range(0, args.frames, args.batch))
     connect = []
     for data, B in batches:
         _, c = module.predict(data, batch_size=B, label=data["labels"].to(torch.uint8), inference=inference)
@@ -106,8 +109,10 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     peek = argparse.ArgumentParser(add_help=False)
     peek.add_argument("--com", default="v2v", type=str)
-    com = peek.parse_known_args(argv)[0].com
-    return comm.run_eval_driver(evaluate if com in OWN_COMS else test_seg.main, argv)
+    peek.add_argument("--scene", default="sampled", type=str)
+    known = peek.parse_known_args(argv)[0]
+    # test_seg.py stays as it is and knows the sampled scene only: a ray-cast evaluation of its three --com runs through the loop above
+    return comm.run_eval_driver(evaluate if known.com in OWN_COMS or known.scene != "sampled" else test_seg.main, argv)
 
 
 if __name__ == "__main__":

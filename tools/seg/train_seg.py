@@ -6,6 +6,7 @@
     python tools/seg/train_seg.py --data /path/V2X-Sim-seg/train --com v2v --nepoch 5 --batch 2 --logpath out/
     python tools/seg/train_seg.py --data synthetic --com when2com --steps 20 --batch 1        (--com: every detection baseline but `late`)
     python tools/seg/train_seg.py --data synthetic --targets boxes --class_weight balanced    (labels rasterized on the GPU, median-frequency weights)
+    python tools/seg/train_seg.py --data synthetic --scene raycast --observed any            (ray-cast world; cells no agent observed are ignored)
 
 Synthetic scenes (utils/synthetic_scene.py: vehicle footprints as class 1), PyTorch-ROCm autograd over the HIP engine's
 parameter tree, checkpoint with upstream's 'model_state_dict' key for tools/seg/test_seg.py / eval_seg.py --resume."""
@@ -23,13 +24,21 @@ import torch  # noqa: E402
 
 
 TARGETS = ("map", "boxes")
+SCENES = ("sampled", "raycast")
+OBSERVED = ("own", "any", "all")
 
 
-def seg_batch(config, frames, agents, seed, device, grid, targets="map", n_classes=8):
+def seg_batch(config, frames, agents, seed, device, grid, targets="map", n_classes=8, scene="sampled", observed="own"):
     """targets="map": the label maps painted per item on the host (synthetic_scene.seg_labels) and uploaded; "boxes": the padded boxes uploaded and
-    rasterized for the whole batch in one call on the device (train/loop.py::seg_targets_on_device, DESIGN.md section 3.8)."""
+    rasterized for the whole batch in one call on the device (train/loop.py::seg_targets_on_device, DESIGN.md section 3.8).
+    scene="raycast": a world of cars (class 1) and walls (class 2) swept on the device, its boxes rasterized there and the cells no ray observed --
+    the sweep's own rays (observed="own"), any agent's of the frame ("any"), or no masking ("all") -- set to the ignore class 255
+    (utils/raycast_scene.raycast_seg_batch_on_device); `targets` does not apply."""
     from v2x_sim_amd import ops
     from v2x_sim_amd.utils import synthetic_scene
+    if scene == "raycast":
+        from v2x_sim_amd.utils import raycast_scene
+        return raycast_scene.raycast_seg_batch_on_device(config, frames, agents, seed, device, observed=observed, n_classes=n_classes, grid=grid)
     b = synthetic_scene.make_batch(frames, agents, seed=seed)
     bits = ops.voxelize_bits(torch.from_numpy(b["points"]).to(device), torch.from_numpy(b["n_pts"]).to(device), grid)
     if targets == "boxes":
@@ -44,11 +53,18 @@ def seg_batch(config, frames, agents, seed, device, grid, targets="map", n_class
 BALANCE_BATCHES = 32     # synthetic data: the class frequencies come from the first 32 batches
 
 
-def synthetic_label_hist(config, frames, agents, first_seed, device, n_classes):
-    """Cells per class over the first BALANCE_BATCHES synthetic batches of a run, from the rasterizer's histogram (only the boxes are uploaded)."""
+def synthetic_label_hist(config, frames, agents, first_seed, device, n_classes, scene="sampled"):
+    """Cells per class over the first BALANCE_BATCHES synthetic batches of a run, from the rasterizer's histogram (only the boxes are uploaded).
+    scene="raycast": the histogram the rasteriser gives for the painted world of each batch, before the unobserved cells are masked."""
     from v2x_sim_amd.train.loop import seg_targets_on_device
     from v2x_sim_amd.utils import synthetic_scene
     total = torch.zeros((n_classes + 1,), dtype=torch.int64, device=device)
+    if scene == "raycast":
+        from v2x_sim_amd.utils import raycast_scene
+        for it in range(BALANCE_BATCHES):
+            total += raycast_scene.raycast_seg_batch_on_device(config, frames, agents, first_seed + it, device, observed="all", n_classes=n_classes,
+                                                               want_hist=True)["hist"].sum(0)
+        return total.cpu().numpy()
     for it in range(BALANCE_BATCHES):
         b = synthetic_scene.make_batch(frames, agents, seed=first_seed + it)
         res = seg_targets_on_device([b["gt_boxes"][a][f] for a in range(agents) for f in range(frames)], None, config, device, n_classes=n_classes,
@@ -120,6 +136,12 @@ def build_parser():
     ap.add_argument("--targets", default="map", choices=list(TARGETS),
                     help="synthetic data: map = label maps painted per item on the host and uploaded; boxes = the boxes uploaded and rasterized for the whole "
                          "batch in one call on the GPU (v2x_seg_rasterize).  A parsed set decides per sample: bev_seg maps or gt_boxes + gt_classes")
+    ap.add_argument("--scene", default="sampled", choices=list(SCENES),
+                    help="synthetic data: sampled = points on every car in range (utils/synthetic_scene.py); raycast = a world of cars and walls swept "
+                         "on the GPU with occlusion, labels rasterized there (cars 1, walls 2) and masked by what the rays observed (--observed)")
+    ap.add_argument("--observed", default="own", choices=list(OBSERVED),
+                    help="--scene raycast: a cell is the ignore class 255 unless a ray of the sweep itself (own) or of any agent of the frame (any) "
+                         "crossed or hit it; all = no masking")
     return ap
 
 
@@ -183,7 +205,7 @@ def main(argv=None):
         if loader is not None:
             hist = dataset_label_hist(dataset, grid, device, model.n_classes)
         else:
-            hist = synthetic_label_hist(config, args.batch, A, (args.seed + start) * 1000003, device, model.n_classes)
+            hist = synthetic_label_hist(config, args.batch, A, (args.seed + start) * 1000003, device, model.n_classes, args.scene)
         class_weight = ops.median_frequency_weights(hist, model.n_classes)
         print("class weights (median frequency): %s" % ", ".join("%.4g" % w for w in class_weight))
     module = SegModule(model, None, config, opt, 0, class_weight=class_weight)
@@ -195,7 +217,8 @@ def main(argv=None):
                 losses.append(module.step(last[0], len(samples[0]), len(samples)))
         else:
             for it in range(args.steps):
-                last = (seg_batch(config, args.batch, A, (args.seed + epoch) * 1000003 + it, device, grid, args.targets, model.n_classes), args.batch)
+                last = (seg_batch(config, args.batch, A, (args.seed + epoch) * 1000003 + it, device, grid, args.targets, model.n_classes, args.scene, args.observed),
+                        args.batch)
                 losses.append(module.step(last[0], A, args.batch))
                 if args.log and it % 20 == 0:
                     print("step %4d  loss %.4f" % (it, losses[-1]), flush=True)

@@ -725,6 +725,7 @@ from .ops_post import assign_targets, assign_targets_sparse_keys, conv2d_det, de
 from .ops_seg import median_frequency_weights, pad_box_lists, rasterize_seg, seg_grid  # noqa: E402,F401
 from .ops_lidar import box_rows, lidar_cast, ring_table, sensor_rows, visible_boxes  # noqa: E402,F401
 from .ops_lidar import az_time_table, lidar_cast_moving, visible_boxes_moving  # noqa: E402,F401
+from .ops_vis import freespace_bits, mask_unobserved, vis_maps  # noqa: E402,F401
 from .ops_track import assign_iou, hota_sequences, mot_sequences, sort_step  # noqa: E402,F401
 from .ops_train import (bn_train_backward, bn_train_forward, cast_pad_chsum, channel_sum, conv3x3_wgrad, det_loss_backward, det_loss_forward,  # noqa: E402,F401
                         det_corner_loss_backward, det_corner_loss_forward, gru_gates, gru_gates_backward, gru_gates_nhwc, gru_gates_nhwc_backward, gru_gates_nhwc_ok, upcat, upcat_backward, v2v_message,

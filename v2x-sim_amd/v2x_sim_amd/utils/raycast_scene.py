@@ -103,14 +103,16 @@ def _ring_on(device, beams, steps, elev_deg=None):
 
 
 def raycast_batch_on_device(config, frames, agents, seed, device, grid=None, anchors=None, with_targets=True, gt="own", min_hits=5, gt_lists=False,
-                            beams=32, steps=2048, max_pts=None, sigma_r=0.02, p_drop=0.0, r_min=1.0, r_max=70.0, step=0, world=None, **world_kw):
+                            beams=32, steps=2048, max_pts=None, sigma_r=0.02, p_drop=0.0, r_min=1.0, r_max=70.0, step=0, world=None, vis_maps=False,
+                            **world_kw):
     """-> the data dict of train.loop.synthetic_batch_on_device (FaFModule.step / predict_all's format) from a ray-cast world, by this chain on the
     device: ops.lidar_cast, ops.visible_boxes, ops.voxelize_bits, ops.bits_to_dense, v2x_det_assign_targets (the IoU rule) --
     straight from the device's padded ground truth; nothing is synchronised.
     gt: "own": an agent's ground truth = the cars inside its BEV extents it got >= min_hits returns from; "any": ... that ANY agent of the frame got
     >= min_hits returns from (the cars the ego cannot see but a neighbour can: where collaboration must help).
     gt_lists: also data["gt_boxes"][agent][frame], host arrays (the one read-back; evaluation wants them).  world: a make_world dict to use instead
-    of make_world(frames, agents, seed, **world_kw)."""
+    of make_world(frames, agents, seed, **world_kw).  vis_maps: also data["vis_maps"] (A * frames, X, Y, Z) fp32, upstream's three-state visibility
+    map of each sweep's own rays (ops.freespace_bits, ops.vis_maps); without it keys and bytes are what they were."""
     import torch
     from .. import ops
     from ..train import loop
@@ -130,12 +132,86 @@ def raycast_batch_on_device(config, frames, agents, seed, device, grid=None, anc
     bits = ops.voxelize_bits(cast["points"], cast["n_pts"], grid)
     data = {"bev_seq": ops.bits_to_dense(bits, grid.dims[2])[:, None], "trans_matrices": torch.from_numpy(world["trans"]).to(device),
             "num_agent": torch.from_numpy(world["num_agent"])}
+    if vis_maps:
+        data["vis_maps"] = ops.vis_maps(bits, ops.freespace_bits(cast["points"], cast["n_pts"], grid), grid.dims[2])
     if gt_lists:
         hb, hc = gt_boxes.cpu().numpy(), gt_count.cpu().numpy()
         data["gt_boxes"] = [[hb[a * frames + f, :hc[a * frames + f]].copy() for f in range(frames)] for a in range(agents)]
     if with_targets:
         anchors = postprocess.build_anchor_map(config) if anchors is None else anchors
         data["labels"], data["reg_targets"], data["reg_loss_mask"] = loop.iou_targets_from_device(gt_boxes, gt_count, anchors, device)
+    return data
+
+
+# ---- segmentation batches -------------------------------------------------------------------------------------------------
+SEG_CAR, SEG_WALL = 1, 2
+OBSERVED = ("own", "any", "all")
+
+
+def fused_jobs(world, frames, agents):
+    """The early-fusion jobs of a frame-major world, as tools/bench_configs.py builds the upperbound's: for every frame f and ego i, one job per agent j
+    moving sweep j * frames + f into grid i * frames + f.  The transform moves POINTS, so it is the geometric one, world["trans_geo"][f, i, j] =
+    inv(P_i) P_j (world["trans"] holds the same poses in the feature warp's axis convention, translation swapped).  -> (xform (n_jobs, 3, 4) f32,
+    src (n_jobs,) i32, dst (n_jobs,) i32) host arrays."""
+    xf, src, dst = [], [], []
+    for f in range(frames):
+        for i in range(agents):
+            for j in range(agents):
+                xf.append(world["trans_geo"][f, i, j][:3])
+                src.append(j * frames + f)
+                dst.append(i * frames + f)
+    return np.ascontiguousarray(np.stack(xf), np.float32), np.asarray(src, np.int32), np.asarray(dst, np.int32)
+
+
+def raycast_seg_batch_on_device(config, frames, agents, seed, device, observed="own", n_classes=8, grid=None, beams=32, steps=2048, max_pts=None,
+                                sigma_r=0.02, p_drop=0.0, r_min=1.0, r_max=70.0, step=0, world=None, want_hist=False, **world_kw):
+    """-> the segmentation batch dict SegModule.step takes (bev_seq, trans_matrices, num_agent, labels (A * frames, X, Y) uint8) from a ray-cast world,
+    by this chain on the device with nothing synchronised: ops.lidar_cast, ops.voxelize_bits, the world's boxes in each agent's frame
+    (ops.visible_boxes_moving with zero velocities, min_hits = 0 and no limits: every box, with its index), ops.rasterize_seg, ops.mask_unobserved.
+    Classes: cars 1 (the ego car too: the box that contains the sensor is dropped by the visibility rule, so it is painted from the world table, at
+    the origin of its own frame), walls 2, everything else 0.  A cell no ray observed -- behind a wall, under a car's far side -- is the ignore class
+    255, the right label for what nobody saw.
+    observed: "own": observed by the sweep's own rays; "any": by the rays of any agent of the frame, walked into the ego grid as fused jobs
+    (fused_jobs; the occupancy that goes with them is ops.voxelize_fused_bits'); "all": no masking -- the painted world.
+    want_hist: also data["hist"] (A * frames, n_classes + 1) int64, the rasteriser's cells per label (before masking)."""
+    import torch
+    from .. import ops
+    if observed not in OBSERVED:
+        raise ValueError("observed must be one of %s" % (OBSERVED,))
+    world = make_world(frames, agents, seed, **world_kw) if world is None else world
+    grid = grid or ops.VoxelGrid(config.voxel_size, config.area_extents)
+    d = world_on_device(world, device)
+    n, cap = agents * frames, world["boxes"].shape[1]
+    beam, az = _ring_on(device, beams, steps)
+    cast = ops.lidar_cast(d["sensors"], d["frame_of"], d["boxes"], d["box_count"], beam, az, max_pts or beams * steps, ground_z=GROUND_Z, r_min=r_min,
+                          r_max=r_max, sigma_r=sigma_r, p_drop=p_drop, seed=seed, step=step, want=("box_hits",))
+    bits = ops.voxelize_bits(cast["points"], cast["n_pts"], grid)
+    # every box of the world -- cars and walls -- in each sweep's frame, with its index
+    zero2 = torch.zeros((n, 2), dtype=torch.float32, device=device)
+    vis = ops.visible_boxes_moving(cast["box_hits"], d["sensors"], zero2, torch.zeros((n,), dtype=torch.float32, device=device), d["frame_of"], d["boxes"],
+                                   torch.zeros((frames, cap, 2), dtype=torch.float32, device=device), d["box_count"], t_ref=0.0, min_hits=0,
+                                   x_lim=1e9, y_lim=1e9, want=())
+    cars = d["car_count"][d["frame_of"].long()][:, None]
+    cls = torch.where(vis["gt_ids"] < cars, SEG_CAR, SEG_WALL).to(torch.uint8)
+    # row 0: the ego car, (0, 0, w, h, 0) in its own frame; sweep m = a * frames + b carries box a of frame b
+    ego = np.zeros((n, 1, 5), np.float32)
+    for a in range(agents):
+        ego[a * frames:(a + 1) * frames, 0, 2:4] = world["boxes"][:, a, 2:4]
+    boxes = torch.cat([torch.from_numpy(ego).to(device), vis["gt_boxes"]], 1)
+    cls = torch.cat([torch.full((n, 1), SEG_CAR, dtype=torch.uint8, device=device), cls], 1)
+    res = ops.rasterize_seg(boxes, cls, vis["gt_count"] + 1, grid, n_classes=n_classes, want=("hist",) if want_hist else ())
+    labels = res["labels"]
+    if observed == "own":
+        ops.mask_unobserved(labels, bits, ops.freespace_bits(cast["points"], cast["n_pts"], grid), out=labels)
+    elif observed == "any":
+        xf, src, dst = (torch.from_numpy(t).to(device) for t in fused_jobs(world, frames, agents))
+        occ = ops.voxelize_fused_bits(cast["points"], cast["n_pts"], xf, src, dst, n, grid)
+        trav = ops.freespace_bits(cast["points"], cast["n_pts"], grid, xform=xf, src_cloud=src, dst_grid=dst, n_grids=n)
+        ops.mask_unobserved(labels, occ, trav, out=labels)
+    data = {"bev_seq": ops.bits_to_dense(bits, grid.dims[2])[:, None], "trans_matrices": torch.from_numpy(world["trans"]).to(device),
+            "num_agent": torch.from_numpy(world["num_agent"]), "labels": labels}
+    if want_hist:
+        data["hist"] = res["hist"]
     return data
 
 
@@ -243,14 +319,16 @@ _AZ_TIMES = {}
 
 def raycast_sequence_on_device(config, world, steps, dt=DT, sweep_time=SWEEP_TIME, device="cuda:0", grid=None, anchors=None, with_targets=True, gt="own",
                                min_hits=5, gt_lists=False, beams=32, az_steps=2048, max_pts=None, sigma_r=0.02, p_drop=0.0, r_min=1.0, r_max=70.0, seed=0,
-                               step=0, elev_deg=None):
+                               step=0, elev_deg=None, vis_maps=False):
     """A sequence of `steps` sweeps, dt apart, of every agent of every world of `world` (make_moving_world), all scenes * steps batch items at once:
     ONE ops.lidar_cast_moving call and ONE ops.visible_boxes_moving call (ground truth at half the sweep duration), then raycast_batch_on_device's
     chain -- voxelise, densify, assign -- with nothing synchronised.  A sweep takes sweep_time; a moving car is met where it is when the beam passes.
     -> the data dict FaFModule.step / predict_all read (bev_seq, trans_matrices, num_agent and, with_targets, the IoU targets), plus gt_ids
     (A * scenes * steps, cap) int32 on the device: the box index of each ground-truth row, the car's identity within its world (-1 past the count),
     and gt_boxes_dev / gt_count, the padded rows themselves.  gt_lists: also gt_boxes[agent][item] and gt_id_lists[agent][item], host arrays (the one
-    read-back), item = w * steps + k.  elev_deg: (lo, hi) elevations of the ring instead of ops.ring_table's."""
+    read-back), item = w * steps + k.  elev_deg: (lo, hi) elevations of the ring instead of ops.ring_table's.  vis_maps: also data["vis_maps"]
+    (A * scenes * steps, X, Y, Z) fp32 as raycast_batch_on_device gives it -- every ray of a raw moving sweep starts at the origin of its own sensor
+    frame, which is what the rule assumes (no de-skewing); without it keys and bytes are what they were."""
     import torch
     from .. import ops
     from ..train import loop
@@ -282,6 +360,8 @@ def raycast_sequence_on_device(config, world, steps, dt=DT, sweep_time=SWEEP_TIM
     bits = ops.voxelize_bits(cast["points"], cast["n_pts"], grid)
     data = {"bev_seq": ops.bits_to_dense(bits, grid.dims[2])[:, None], "trans_matrices": torch.from_numpy(seq["trans"]).to(device),
             "num_agent": torch.from_numpy(seq["num_agent"]), "gt_ids": vis["gt_ids"], "gt_boxes_dev": vis["gt_boxes"], "gt_count": vis["gt_count"]}
+    if vis_maps:
+        data["vis_maps"] = ops.vis_maps(bits, ops.freespace_bits(cast["points"], cast["n_pts"], grid), grid.dims[2])
     if gt_lists:
         hb, hc, hi = vis["gt_boxes"].cpu().numpy(), vis["gt_count"].cpu().numpy(), vis["gt_ids"].cpu().numpy()
         data["gt_boxes"] = [[hb[a * B + j, :hc[a * B + j]].copy() for j in range(B)] for a in range(A)]
