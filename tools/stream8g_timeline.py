@@ -22,21 +22,32 @@ def main():
     fetch = lib.v2x_debug_stream_timeline
     fetch.restype, fetch.argtypes = C.c_int, [C.c_void_p]
     dev = torch.device("cuda:0")
-    for name, cin, cout, hw, n in (("384->128 @64 (36 steps per tile)", 384, 128, 64, 320), ("128->128 @64 (12 steps per tile)", 128, 128, 64, 320),
-                                   ("768->256 @32 (72 steps per tile)", 768, 256, 32, 320)):
-        w = torch.randn(cout, cin, 3, 3) * 0.05
-        pc = packing.pack_conv_stream(name, w, torch.ones(cout), torch.zeros(cout), C0=cin, relu=True, device=dev)
-        x = torch.randn(n, hw, hw, cin, device=dev).to(torch.bfloat16)
+    cases = (("384->128 @64 (36 steps per tile)", 384, 128, 64, 320), ("128->128 @64 (12 steps per tile)", 128, 128, 64, 320),
+             ("768->256 @32 (72 steps per tile)", 768, 256, 32, 320))
+    if "gru" in sys.argv[1:]:       # the ConvGRU's shape only (96-row tiles: 72 MFMAs per phase, two plain sources): python3 tools/stream8g_timeline.py gru
+        cases = (("ConvGRU 256 + 256 -> 3 x 256 @32 (48 steps per tile)", 512, 256, 32, 320),)
+    for name, cin, cout, hw, n in cases:
+        gru = name.startswith("ConvGRU")
+        x1 = None
+        if gru:
+            w = torch.randn(3 * cout, cin, 3, 3) * 0.02
+            pc = packing.pack_gru_stream(name, w, torch.randn(3 * cout) * 0.1, torch.randn(3 * cout) * 0.1, C0=cin // 2, C1=cin // 2, device=dev)
+            x = torch.relu(torch.randn(n, hw, hw, cin // 2, device=dev)).to(torch.bfloat16)
+            x1 = torch.relu(torch.randn(n, hw, hw, cin // 2, device=dev)).to(torch.bfloat16)
+        else:
+            w = torch.randn(cout, cin, 3, 3) * 0.05
+            pc = packing.pack_conv_stream(name, w, torch.ones(cout), torch.zeros(cout), C0=cin, relu=True, device=dev)
+            x = torch.randn(n, hw, hw, cin, device=dev).to(torch.bfloat16)
         for _ in range(3):
-            y = ops.conv2d(pc, x)
+            y = ops.conv2d(pc, x, x1)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        y = ops.conv2d(pc, x)
+        y = ops.conv2d(pc, x, x1)
         e1.record()
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) * 1e3
-        flops = 2.0 * n * hw * hw * cout * 9 * cin
+        flops = 2.0 * n * hw * hw * cout * 9 * cin * (3 if gru else 1)
         buf = np.zeros(2 * 128 * 4, dtype=np.uint32)
         rc = fetch(buf.ctypes.data_as(C.c_void_p))
         assert rc == 0, rc
@@ -53,8 +64,8 @@ def main():
             bar2 = tg[1:, 0] - tg[:-1, 3]
             period = tg[1:, 0] - tg[:-1, 0]
             sl = slice(4, k - 1)
-            print("  group %d (%s): period %.0f ns | load phase %.0f | wait at barrier 1 %.0f | MFMA phase (96 MFMAs) %.0f | barrier 2 + loop %.0f   [median period %.0f, max %.0f]"
-                  % (g, "patch filler" if g == 0 else "weight streamer", period[sl].mean(), load[sl].mean(), bar1[sl].mean(), mfma[sl].mean(), bar2[sl].mean(),
+            print("  group %d (%s): period %.0f ns | load phase %.0f | wait at barrier 1 %.0f | MFMA phase (%d MFMAs) %.0f | barrier 2 + loop %.0f   [median period %.0f, max %.0f]"
+                  % (g, "patch filler" if g == 0 else "weight streamer", period[sl].mean(), load[sl].mean(), bar1[sl].mean(), 72 if gru else 96, mfma[sl].mean(), bar2[sl].mean(),
                      np.median(period[sl]), period[sl].max()))
         # tile boundaries (round 4): steps S3 - 1 -> S3: "barrier 2 + loop" of the last step of a tile contains the epilogue, its stores and the tile switch
         S3 = 3 * cin // 32

@@ -790,10 +790,14 @@ int v2x_num_cus() {   // also used by conv_halo_pair.hip
 // the load phase's DMA issue of conv3x3_stream8g_kernel (a macro, not a lambda: captured by reference, `pd` and `nw` went to scratch)
 #define V2X_STREAM8G_ISSUE_DMAS \
                 if (grp == 1) { \
-                    const int ahead = st + 2; \
-                    const int wslot = slot == 0 ? 2 : slot - 1; \
-                    if (ahead < S3) nw = issue_weights(ahead, wslot, wv, 4); \
-                    else if (has_next && ahead - S3 < S3) nw = issue_weights(ahead - S3, wslot, wv, 4); \
+                    if constexpr (LP96) { \
+                        if (kx == 0 || fill) nw = issue_weights96(kx == 0 ? wc0 : wc1, (kx + 2) % 3); \
+                    } else { \
+                        const int ahead = st + 2; \
+                        const int wslot = slot == 0 ? 2 : slot - 1; \
+                        if (ahead < S3) nw = issue_weights(ahead, wslot, wv, 4); \
+                        else if (has_next && ahead - S3 < S3) nw = issue_weights(ahead - S3, wslot, wv, 4); \
+                    } \
                 } else if (fill && kx < 2) { \
                     const int npieces = hfn ? (PH0 * PW0 * 4 + 63) / 64 : PATCH8_PIECES; \
 _Pragma("unroll") \
@@ -827,6 +831,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // output-store instructions per wave and tile (the counted waits after an epilogue leave exactly these in flight): 8-byte stores per
     // (16-channel tile, 16-pixel fragment)
     constexpr int N_ST = (EPI == SEPI_GRU) ? (TCO / 3) * 2 : TCO * 2;   // dwordx4 stores (stream_epilogue X4); on the dwordx2 path (unaligned rows) the counted wait is merely stricter
+    // LP96: the 96-row form (the ConvGRU) has 32 accumulator registers fewer than the 128-row form, and its load phase is as long as its 72-MFMA
+    // phase.  Its kx loop is UNROLLED, so the step position (tap column, ring slot = kx, patch piece numbers) is a compile-time constant: the
+    // descriptor select chain, the ring-slot arithmetic and the kx tests fold away; the lane parts of the fragment and weight addresses are
+    // hoisted (column table, weight-row offset, 8 registers), and the weight DMAs take a per-chunk scalar base + per-wave scalar offsets
+    // instead of divisions by 3 and by W_PIECES in every step.  Same DMAs, same reads, same order: bit-identical.
+    constexpr bool LP96 = (BCO == 96);
+    constexpr int KXU = LP96 ? 3 : 1;                      // unroll count of the kx loop
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *s_ring = smem;                                   // 3 x STEP_BYTES
@@ -881,6 +892,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         return cnt;
     };
+    // LP96: the same pieces from scalars.  Piece p = wv + 4u of a step lies p KiB into its ring slot (a tap slice is W_PIECES KiB), and
+    // (tap row ky = p / W_PIECES) * 2 slices + p KiB behind the step's first slice (chunk, ky = 0, kx) in the packed weights (tap rows are 3
+    // slices apart).  The wave's KiB and the lane's 16 bytes are one hoisted register, the rest is wave-uniform: woff96(u).
+    const unsigned wl_off = LP96 ? (unsigned)((wv * 64 + lane) * 16) : 0u;
+    auto woff96 = [&](int u) -> int { return ((wv + 4 * u) / W_PIECES) * (2 * SLICE_BYTES) + u * 4096; };
+    const int nw96 = LP96 ? (3 * W_PIECES - wv + 3) / 4 : 0;   // pieces of this wave per step
+    auto issue_weights96 = [&](const uint16_t *chunk_w, int kxa) -> int {   // the chunk's packed weights, tap column (= ring slot) kxa
+        const char *src = reinterpret_cast<const char *>(chunk_w) + kxa * SLICE_BYTES;
+        char *dst = s_ring + kxa * STEP_BYTES + wv * 1024;
+#pragma unroll
+        for (int u = 0; u < NWD; ++u) {
+            if (u >= nw96) break;                          // wave-uniform
+            glds16s_aux<V2X_STREAM8G_WEIGHT_AUX>(src + woff96(u) + wl_off, dst + u * 4096);
+        }
+        return nw96;
+    };
     // wait until at most `keep` vector-memory operations are outstanding, keep in {0, NWD-1, NWD} (+ N_ST): the immediate must be
     // a constant, the choice is wave-uniform
     auto wait_keep = [&](int keep, bool plus_stores) {
@@ -901,6 +928,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int f = 0; f < NF; ++f) frow[f] = R0 + (f >> 1);
     const bool chunk0_half = (nc0 > 0) && a.up0;
+    // LP96 lane constants: ct[ch][kx], the byte offset inside a patch row of the pixel fragment of columns ch * 16 + fj under tap column kx
+    // (for the source resolution ct_half); the lane's place in a weight slice
+    int ct[2][3];
+    bool ct_half = chunk0_half;
+    if constexpr (LP96) patch_col_table<2, TW, PSH>(ct, fj, fq, ct_half);
+    const int a_off96 = LP96 ? (fq * BCO + fj) * 16 + coh * (HCO * 256) : 0;
 
     int tile = bid;
     int n, y0, x0;
@@ -996,10 +1029,25 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int sh = half ? 1 : 0;
             const int row_bytes = (half ? PW0 : PW) * 64;
             const int row0 = (R0 >> sh) * row_bytes;            // the wave's first patch row
-#pragma unroll 1   // rolled: unrolled copies of this body hoist ~100 lane constants and spill
+            // LP96: the chunk's packed weights and the next chunk's (the next tile's first: same channel tile, same weights); the column
+            // table follows the source resolution
+            const uint16_t *wc0 = LP96 ? wbase + (size_t)kc * 9 * (BCO * 32) : wbase;
+            const uint16_t *wc1 = LP96 ? wbase + (size_t)kcn * 9 * (BCO * 32) : wbase;
+            int pbrow = 0, rq[NB / 2] = {};                      // LDS offset of the wave's first patch row; patch row q behind it (scalars)
+            if constexpr (LP96) {
+                if (half != ct_half) {                           // wave-uniform
+                    patch_col_table<2, TW, PSH>(ct, fj, fq, half);
+                    ct_half = half;
+                }
+                pbrow = __builtin_amdgcn_readfirstlane(3 * STEP_BYTES + (gc & 1) * PATCH8_BYTES + row0);
+#pragma unroll
+                for (int q = 0; q < NB / 2; ++q) rq[q] = __builtin_amdgcn_readfirstlane((((q - sh) >> sh) + sh) * row_bytes);
+            }
+            // rolled at 128 rows: unrolled copies of this body hoist ~100 lane constants and spill
+#pragma unroll KXU
             for (int kx = 0; kx < 3; ++kx, ++g, slot = (slot == 2 ? 0 : slot + 1)) {
                 const int st = kc * 3 + kx;
-                const int ln = fresh_lane();
+                const int ln = LP96 ? 0 : fresh_lane();
                 const int fjl = ln & 15, fql = ln >> 4;
                 // ---- L: group 1 streams the weights of step st+2 (wrapping into the next tile), group 0 the next chunk's patch
                 int nw = 0;   // weight DMAs this wave issues in this phase
@@ -1009,15 +1057,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 bf16x8_t B[NB];
 #pragma unroll
                 for (int ch = 0; ch < 2; ++ch) {
-                    const int col = ch * 16 + fjl + kx;
-                    const int pc = ((col - sh) >> sh) + sh;     // full: col + kx;  half: ((col + kx - 1) >> 1) + 1
-                    const int coff = ((pc << 2) + (fql ^ ((pc >> PSH) & 3))) * 16;
+                    if constexpr (LP96) {   // hoisted column offset + scalars
+                        const int c0 = ct[ch][kx] + pbrow;
 #pragma unroll
-                    for (int q = 0; q < NB / 2; ++q) {
-                        B[q * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(pb + row0 + (((q - sh) >> sh) + sh) * row_bytes + coff);
+                        for (int q = 0; q < NB / 2; ++q) B[q * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(smem + (c0 + rq[q]));
+                    } else {
+                        const int col = ch * 16 + fjl + kx;
+                        const int pc = ((col - sh) >> sh) + sh;     // full: col + kx;  half: ((col + kx - 1) >> 1) + 1
+                        const int coff = ((pc << 2) + (fql ^ ((pc >> PSH) & 3))) * 16;
+#pragma unroll
+                        for (int q = 0; q < NB / 2; ++q) {
+                            B[q * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(pb + row0 + (((q - sh) >> sh) + sh) * row_bytes + coff);
+                        }
                     }
                 }
-                const char *ws = s_ring + slot * STEP_BYTES + (fql * BCO + fjl) * 16 + coh * (HCO * 256);   // + compile-time offsets below
+                // (LP96: the ring slot of a step is its tap column -- a tile is a whole number of chunks)
+                const char *ws = LP96 ? s_ring + kx * STEP_BYTES + a_off96
+                                      : s_ring + slot * STEP_BYTES + (fql * BCO + fjl) * 16 + coh * (HCO * 256);   // + compile-time offsets below
                 bf16x8_t A[2][WT ? BT : HCO];                    // two alternating sets: the next block's fragments land under this block's MFMAs
 #pragma unroll
                 for (int i = 0; i < (WT ? BT : HCO); ++i) A[0][i] = *reinterpret_cast<const bf16x8_t *>(ws + i * 256);
@@ -1026,7 +1082,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 // the tile's output stores are younger than those and may stay in flight); group 0 -- at kx = 2, the patch it issued
                 // during kx = 0, 1 (two to four intervals ago), together with any older stores
                 if (grp == 1) {
-                    wait_keep(nw, relaxed);
+                    if constexpr (LP96) {   // the steady state first (the wave's own pieces of this phase stay in flight, no stores): two branches instead of a chain
+                        if (nw != 0 && !relaxed) {
+                            if (nw96 == NWD) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWD) : "memory");
+                            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWD - 1) : "memory");
+                        } else {
+                            wait_keep(nw, relaxed);
+                        }
+                    } else {
+                        wait_keep(nw, relaxed);
+                    }
                     relaxed = false;
                 } else if (kx == 2) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
