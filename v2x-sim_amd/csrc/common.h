@@ -11,6 +11,14 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
+// 16 B per lane, global -> LDS without a VGPR round trip (global_load_lds_dwordx4), for every conv family.  The LDS destination is the wave-uniform
+// base + lane * 16, so any swizzle lives in the per-lane SOURCE address.
+typedef const __attribute__((address_space(1))) void *gptr_t;
+typedef __attribute__((address_space(3))) void *lptr_t;
+__device__ __forceinline__ void glds16(const void *g, char *lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
+}
+
 // thread-local error text behind v2x_last_error()
 void v2x_set_error(const char *fmt, ...);
 

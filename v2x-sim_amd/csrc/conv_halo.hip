@@ -23,17 +23,10 @@
 //     the second MFMA (hidden channel kappa = 32*(i>>1) + 8*q + 4*(i&1) + r for tile i, lane group q,
 //     register r) -- no cross-lane traffic, the hidden map never exists in memory.
 #include "common.h"
+#include "halo_geom.h"   // tile / patch geometry, the patch layout and its table word, the zero page
 #include <cstdlib>
 
-// 64 B of zeros for out-of-image patch pixels (own copy: no relocatable device code needed)
-static __device__ __attribute__((aligned(64))) unsigned int g_zero_page_h[16];
-
-typedef const __attribute__((address_space(1))) void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
-
-__device__ __forceinline__ void glds16h(const void *g, char *lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
+using namespace halo;   // TH x TW output tile, PH x PW / PH0 x PW0 patches, slot counts
 
 struct HaloArgs {
     const uint16_t *in0;  // [N][H/2][W/2][C0] (nearest-x2 upsampled on the fly) or nullptr
@@ -61,35 +54,6 @@ struct HaloArgs {
     int x4;               // bf16 outputs: 16-byte stores (common.h: v2x_store_pair_x4); set by the dispatch when the output view allows
 };
 
-constexpr int TH = 8, TW = 32, PH = TH + 2, PW = TW + 2;
-constexpr int PH0 = TH / 2 + 2, PW0 = TW / 2 + 2;
-
-// Patch swizzle (slot permutation per pixel x).  Chosen by TIMING the fragment reads (tools/lds_conflict_probe.hip: lane (fj, fq) reads
-// 16 bytes of pixel x0 + fj -- or ((c + fj) >> 1) + 1 for a half-resolution source -- at slot 4*kc + fq; 8 reads in flight per wave):
-//   4 slots per pixel:  (x >> 2) & 3             17.5 ns per read at every alignment of both forms;  the round-1 choice (x >> 1) & 3:
-//                                                22.9 ns for EVERY full-resolution read, 22.6 for two of three half-resolution alignments
-//   8 slots per pixel:  ((x >> 1) & 1) * 4 ^ ((x >> 2) & 3)   17.2-17.5 ns;  round 1's x & 7: 22.7 / 19.2 ns
-// SQ_LDS_BANK_CONFLICT reads 0 for the slow full-resolution patterns: the counter does not see whatever pairing rule ds_read_b128
-// applies, which is how round 1's search (driven by that counter) settled on them.  INSIDE the kernels the faster reads change nothing
-// (same-box A/B, two runs each: heads 1 132-1 154 vs 1 133-1 139 us, conv8_1 967-974 vs 975-977, pair kernel 687-713 vs 723-727 (worse: its
-// layer-A epilogue WRITES this layout), conv7_2 365-367 vs 364-369): the fragment reads are not what these kernels wait for.  Default stays
-// the round-1 swizzle (V2X_HALO_PSWZ_BUILD=1); =2 builds the timing-derived one.
-#ifndef V2X_HALO_PSWZ_BUILD
-#define V2X_HALO_PSWZ_BUILD 1
-#endif
-template <int SPP>
-__device__ __forceinline__ int swz(int slot, int x) {
-    if constexpr (V2X_HALO_PSWZ_BUILD == 1) {
-        if constexpr (SPP == 8) return slot ^ (x & 7);
-        else return slot ^ ((x >> 1) & 3);
-    } else {
-        if constexpr (SPP == 8) return slot ^ ((((x >> 1) & 1) << 2) ^ ((x >> 2) & 3));
-        else return slot ^ ((x >> 2) & 3);  // SPP 4 or 12: permute inside each aligned group of 4 slots
-    }
-}
-
-constexpr int round64(int v) { return (v + 63) / 64 * 64; }
-
 // EPI2: 0 = none (plain epilogue, bf16 out), 1 = chained 1x1 with bf16 out, 2 = chained 1x1 with fp32 split out,
 //       3 = detection heads: the chained 1x1's rows are in "det order" (include/v2x_amd.h, V2X_EPI_DET) so that lane (fj, fq < 3) holds
 //           the two class logits AND the six box codes of anchors 2 fq and 2 fq + 1 of its pixel; the foreground score is thresholded
@@ -107,8 +71,7 @@ constexpr int round64(int v) { return (v + 63) / 64 * 64; }
 template <int C0, int C1, int COUT, int COUT2, int EPI2, bool DB, bool BITS = false>
 __device__ __forceinline__ void conv3x3_halo_body(const HaloArgs &a) {
     constexpr int SPP0 = C0 / 8, SPP1 = C1 / 8;
-    constexpr int NS1 = round64(PH * PW * SPP1);            // 16-B slots of the full-res patch (padded to whole waves)
-    constexpr int NS0 = C0 ? round64(PH0 * PW0 * SPP0) : 0; // ... of the half-res patch
+    constexpr int NS1 = ns1(C1), NS0 = ns0(C0);   // 16-B slots of the full-res / half-res patch (padded to whole waves)
     constexpr int PATCH_BYTES = (NS0 + NS1) * 16;
     constexpr int KSLOTS = 9 * (SPP0 + SPP1);
     constexpr int W_BYTES = KSLOTS * COUT * 16;
@@ -143,44 +106,27 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloArgs &a) {
     const int fq = lane >> 4;  // k-group (operands) / channel quad (accumulators)
 
     // ---- weights: one linear LDS-DMA copy, resident for the whole kernel --------------------------
-    for (int off = wave * 1024; off < W_BYTES; off += 4096)
-        glds16h(reinterpret_cast<const char *>(a.w) + off + lane * 16, s_w + off);
+    for (int off = wave * 1024; off < W_BYTES; off += 4096) glds16(reinterpret_cast<const char *>(a.w) + off + lane * 16, s_w + off);
 
-    // ---- per-lane DMA tables, computed once (the per-tile patch fill is then ~14 instructions per 1-KiB piece instead
-    // of ~60: two integer divisions by constants, the swizzle and the 64-bit address used to be redone for every piece
-    // of every tile -- ~560 of the ~1200 instructions a wave executed per conv8_1 tile).  Piece t of this wave covers
-    // LDS slots [wave*64 + t*256, +64); one packed word per piece: bits 0-19 = element offset of the lane's 16 B relative
-    // to the patch origin pixel (the dispatcher bounds W so that it fits), bits 20-23 = patch row, bits 24-29 = patch
-    // column (for the image-bounds test), negative = padding slot behind the patch.
+    // ---- per-lane DMA tables (halo_geom.h: halo_entry), computed once (the per-tile patch fill is then ~14 instructions per
+    // 1-KiB piece instead of ~60: two integer divisions by constants, the swizzle and the 64-bit address used to be redone for
+    // every piece of every tile -- ~560 of the ~1200 instructions a wave executed per conv8_1 tile).  Piece t of this wave covers
+    // LDS slots [wave*64 + t*256, +64); one packed word per piece.
     constexpr bool TABLES = DB && !BITS;   // the single-buffer form lives on a 128-VGPR budget: it keeps the per-piece arithmetic
     constexpr int NP1 = TABLES ? (NS1 + 255) / 256 : 0, NP0 = TABLES ? (NS0 + 255) / 256 : 0;
     int tb1[NP1 ? NP1 : 1], tb0[NP0 ? NP0 : 1];
     if constexpr (TABLES) {
 #pragma unroll
-        for (int t = 0; t < NP1; ++t) {
-            const int L = wave * 64 + t * 256 + lane;
-            const int pix = L / SPP1, phys = L - pix * SPP1;
-            const int pr = pix / PW, pc = pix - pr * PW;
-            tb1[t] = pix < PH * PW ? (((pr * a.W + pc) * C1 + swz<SPP1>(phys, pc) * 8) | (pr << 20) | (pc << 24)) : -1;
-        }
+        for (int t = 0; t < NP1; ++t) tb1[t] = halo_entry<PH, PW, SPP1>(a.W, C1, wave * 64 + t * 256 + lane);
         if constexpr (C0 > 0) {
-            constexpr int S0 = SPP0 ? SPP0 : 1;
 #pragma unroll
-            for (int t = 0; t < NP0; ++t) {
-                const int L = wave * 64 + t * 256 + lane;
-                const int pix = L / S0, phys = L - pix * S0;
-                const int pr = pix / PW0, pc = pix - pr * PW0;
-                tb0[t] = pix < PH0 * PW0 ? (((pr * (a.W >> 1) + pc) * C0 + swz<(SPP0 ? SPP0 : 4)>(phys, pc) * 8) | (pr << 20) | (pc << 24)) : -1;
-            }
+            for (int t = 0; t < NP0; ++t) tb0[t] = halo_entry<PH0, PW0, SPP0, 1>(a.W, C0, wave * 64 + t * 256 + lane);
         }
     }
 
     auto load_patch = [&](int tile, int buf) {
-        const int txy = a.tiles_x * a.tiles_y;
-        const int n = tile / txy;
-        const int r = tile - n * txy;
-        const int ty = r / a.tiles_x;
-        const int tx = r - ty * a.tiles_x;
+        int n, ty, tx;
+        halo_tile_index(a.tiles_x, a.tiles_x * a.tiles_y, tile, n, ty, tx);
         const int y0 = ty * TH, x0 = tx * TW;
         char *pb = s_patch + buf * PATCH_BYTES;
         if constexpr (BITS) {
@@ -200,7 +146,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloArgs &a) {
                     v.y = ((b & 4u) ? one : 0u) | ((b & 8u) ? (one << 16) : 0u);
                     v.z = ((b & 16u) ? one : 0u) | ((b & 32u) ? (one << 16) : 0u);
                     v.w = ((b & 64u) ? one : 0u) | ((b & 128u) ? (one << 16) : 0u);
-                    *reinterpret_cast<uint4 *>(pb + NS0 * 16 + (p * 4 + swz<4>(slot, pc)) * 16) = v;
+                    *reinterpret_cast<uint4 *>(pb + NS0 * 16 + halo_pix_off<4>(p, pc, slot)) = v;
                 }
             }
             return;
@@ -209,28 +155,26 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloArgs &a) {
             // full-resolution source: patch pixel (pr, pc) <- image pixel (y0-1+pr, x0-1+pc)
             for (int base = wave * 64; base < NS1; base += 256) {
                 const int L = base + lane;
-                const int pix = L / SPP1;
-                const int phys = L - pix * SPP1;
-                const int pr = pix / PW;
-                const int pc = pix - pr * PW;
+                const int pix = L / SPP1, phys = L - pix * SPP1;
+                const int pr = pix / PW, pc = pix - pr * PW;
                 const int y = y0 - 1 + pr, x = x0 - 1 + pc;
                 const bool ok = pix < PH * PW && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-                const unsigned off = ((unsigned)(n * a.H + y) * (unsigned)a.W + (unsigned)x) * (unsigned)C1 + swz<SPP1>(phys, pc) * 8;
-                glds16h(ok ? (const void *)(a.in1 + off) : (const void *)g_zero_page_h, pb + NS0 * 16 + base * 16);
+                const unsigned off = ((unsigned)(n * a.H + y) * (unsigned)a.W + (unsigned)x) * (unsigned)C1 + halo_swz<SPP1>(phys, pc) * 8;
+                glds16(ok ? (const void *)(a.in1 + off) : (const void *)g_halo_zero_page, pb + NS0 * 16 + base * 16);
             }
             static_assert(TABLES || C0 == 0, "the single-buffer form has one source");
             return;
         }
         // full-resolution source: patch pixel (pr, pc) <- image pixel (y0-1+pr, x0-1+pc)
         {
-            const unsigned base = ((unsigned)(n * a.H + y0 - 1) * (unsigned)a.W + (unsigned)(x0 - 1)) * (unsigned)C1;  // may wrap: only used in-bounds
+            const unsigned base = ((unsigned)(n * a.H + y0 - 1) * (unsigned)a.W + (unsigned)(x0 - 1)) * (unsigned)C1;   // element offset of the patch's first source pixel (may wrap: only used in-bounds)
 #pragma unroll
             for (int t = 0; t < NP1; ++t) {
                 if (wave * 64 + t * 256 >= NS1) break;   // wave-uniform
-                const int y = y0 - 1 + ((tb1[t] >> 20) & 15), x = x0 - 1 + ((tb1[t] >> 24) & 63);
+                const int y = y0 - 1 + halo_entry_row(tb1[t]), x = x0 - 1 + halo_entry_col(tb1[t]);
                 const bool ok = tb1[t] >= 0 && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-                const unsigned off = base + (unsigned)(tb1[t] & 0xfffff);
-                glds16h(ok ? (const void *)(a.in1 + off) : (const void *)g_zero_page_h, pb + NS0 * 16 + (wave * 64 + t * 256) * 16);
+                const unsigned off = base + halo_entry_off(tb1[t]);
+                glds16(ok ? (const void *)(a.in1 + off) : (const void *)g_halo_zero_page, pb + NS0 * 16 + (wave * 64 + t * 256) * 16);
             }
         }
         if constexpr (C0 > 0) {
@@ -240,10 +184,11 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloArgs &a) {
 #pragma unroll
             for (int t = 0; t < NP0; ++t) {
                 if (wave * 64 + t * 256 >= NS0) break;   // wave-uniform
+                // (the table word's fields taken apart in place: through halo_entry_row / _col / _off this one loop compiles to selects, not to the branches it had)
                 const int y = (y0 >> 1) - 1 + ((tb0[t] >> 20) & 15), x = (x0 >> 1) - 1 + ((tb0[t] >> 24) & 63);
                 const bool ok = tb0[t] >= 0 && (unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws;
                 const unsigned off = base + (unsigned)(tb0[t] & 0xfffff);
-                glds16h(ok ? (const void *)(a.in0 + off) : (const void *)g_zero_page_h, pb + (wave * 64 + t * 256) * 16);
+                glds16(ok ? (const void *)(a.in0 + off) : (const void *)g_halo_zero_page, pb + (wave * 64 + t * 256) * 16);
             }
         }
     };
@@ -350,8 +295,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloArgs &a) {
                     for (int ch = 0; ch < 2; ++ch) {
                         const int pr = wave + hr;                           // = ((2w + r + ky - 1) >> 1) + 1
                         const int pc = ((ch * 16 + fj + kx - 1) >> 1) + 1;
-                        F.B[hr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(
-                            pb + ((pr * PW0 + pc) * (SPP0 ? SPP0 : 1) + swz<(SPP0 ? SPP0 : 4)>(kk * 4 + fq, pc)) * 16);
+                        F.B[hr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(pb + ((pr * PW0 + pc) * SPP0 + halo_swz<SPP0>(kk * 4 + fq, pc)) * 16);
                     }
             } else {
                 const int kc = kk - KC0;
@@ -368,8 +312,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloArgs &a) {
                     for (int ch = 0; ch < 2; ++ch) {
                         const int pr = 2 * wave + rr;                       // = 2w + r + ky
                         const int pc = ch * 16 + fj + kx;
-                        F.B[rr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(
-                            pb + NS0 * 16 + ((pr * PW + pc) * SPP1 + swz<SPP1>(kc * 4 + fq, pc)) * 16);
+                        F.B[rr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(pb + NS0 * 16 + ((pr * PW + pc) * SPP1 + halo_swz<SPP1>(kc * 4 + fq, pc)) * 16);
                     }
             }
         };
@@ -406,11 +349,8 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloArgs &a) {
         }
 
         // ---- epilogue -----------------------------------------------------------------------------
-        const int txy = a.tiles_x * a.tiles_y;
-        const int n = tile / txy;
-        const int rr = tile - n * txy;
-        const int ty = rr / a.tiles_x;
-        const int tx = rr - ty * a.tiles_x;
+        int n, ty, tx;
+        halo_tile_index(a.tiles_x, a.tiles_x * a.tiles_y, tile, n, ty, tx);
         if constexpr (EPI2 == 3) {
             static_assert(EPI2 != 3 || (C0 == 0 && C1 == 32 && COUT == 64 && COUT2 == 64), "detection heads: 32 -> (32 | 32) -> det order");
             auto hidden = [&](const f32x4_t &lo, const f32x4_t &hi, const float4 &s0, const float4 &t0, const float4 &s1, const float4 &t1) {
@@ -465,8 +405,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const HaloArgs &a) {
 #pragma unroll
                         for (int ky = 0; ky < 3; ++ky) {
                             const int kslot = (ky * 3 + kx) * SPP1 + fq;
-                            const int pr = 2 * wave + r + ky, pc = ch * 16 + fj + kx;
-                            const bf16x8_t Bf = *reinterpret_cast<const bf16x8_t *>(pb + NS0 * 16 + ((pr * PW + pc) * SPP1 + swz<SPP1>(fq, pc)) * 16);
+                            const bf16x8_t Bf = *reinterpret_cast<const bf16x8_t *>(pb + NS0 * 16 + halo_frag_off_full<SPP1>(2 * wave + r + ky, ch * 16 + fj, kx, fq));
                             const bf16x8_t A2 = *reinterpret_cast<const bf16x8_t *>(s_w + (kslot * COUT + 32 + fj) * 16);
                             const bf16x8_t A3 = *reinterpret_cast<const bf16x8_t *>(s_w + (kslot * COUT + 48 + fj) * 16);
                             g2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A2, Bf, g2, 0, 0, 0);
@@ -671,8 +610,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 template <int C0, int C1, int COUT, int COUT2 = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_halo_pp_kernel(const HaloArgs a) {
     constexpr int SPP0 = C0 / 8, SPP1 = C1 / 8;
-    constexpr int NS1 = round64(PH * PW * SPP1);
-    constexpr int NS0 = C0 ? round64(PH0 * PW0 * SPP0) : 0;
+    constexpr int NS1 = ns1(C1), NS0 = ns0(C0);
     constexpr int PATCH_BYTES = (NS0 + NS1) * 16;
     constexpr int KSLOTS = 9 * (SPP0 + SPP1);
     constexpr int W_BYTES = KSLOTS * COUT * 16;
@@ -706,8 +644,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int fj = lane & 15, fq = lane >> 4;
     char *pb = s_patch + grp * PATCH_BYTES;
 
-    for (int off = wave * 1024; off < W_BYTES; off += 8192)
-        glds16h(reinterpret_cast<const char *>(a.w) + off + lane * 16, s_w + off);
+    for (int off = wave * 1024; off < W_BYTES; off += 8192) glds16(reinterpret_cast<const char *>(a.w) + off + lane * 16, s_w + off);
 
     // per-lane DMA tables (see conv3x3_halo_body): piece t of wave wv of a group covers patch slots [wv*64 + t*256, +64)
     // (the chained form recomputes them per piece instead: its store phase has slack next to the other group's MFMA interval,
@@ -716,43 +653,25 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr int NP1 = (NS1 + 255) / 256, NP0 = (NS0 + 255) / 256;
     int tb1[TABLES ? NP1 : 1], tb0[NP0 ? NP0 : 1];
 #pragma unroll
-    for (int t = 0; t < (TABLES ? NP1 : 0); ++t) {
-        const int L = wv * 64 + t * 256 + lane;
-        const int pix = L / SPP1, phys = L - pix * SPP1;
-        const int pr = pix / PW, pc = pix - pr * PW;
-        tb1[t] = pix < PH * PW ? (((pr * a.W + pc) * C1 + swz<SPP1>(phys, pc) * 8) | (pr << 20) | (pc << 24)) : -1;
-    }
+    for (int t = 0; t < (TABLES ? NP1 : 0); ++t) tb1[t] = halo_entry<PH, PW, SPP1>(a.W, C1, wv * 64 + t * 256 + lane);
     if constexpr (C0 > 0) {
-        constexpr int S0 = SPP0 ? SPP0 : 1;
 #pragma unroll
-        for (int t = 0; t < NP0; ++t) {
-            const int L = wv * 64 + t * 256 + lane;
-            const int pix = L / S0, phys = L - pix * S0;
-            const int pr = pix / PW0, pc = pix - pr * PW0;
-            tb0[t] = pix < PH0 * PW0 ? (((pr * (a.W >> 1) + pc) * C0 + swz<(SPP0 ? SPP0 : 4)>(phys, pc) * 8) | (pr << 20) | (pc << 24)) : -1;
-        }
+        for (int t = 0; t < NP0; ++t) tb0[t] = halo_entry<PH0, PW0, SPP0, 1>(a.W, C0, wv * 64 + t * 256 + lane);
     }
 
     const int txy = a.tiles_x * a.tiles_y;
-    auto coords = [&](int tile, int &n, int &y0, int &x0) {
-        n = tile / txy;
-        const int r = tile - n * txy;
-        const int ty = r / a.tiles_x;
-        y0 = ty * TH;
-        x0 = (r - ty * a.tiles_x) * TW;
-    };
+    auto coords = [&](int tile, int &n, int &y0, int &x0) { px_tile_coords<TH, TW>(a.tiles_x, txy, tile, n, y0, x0); };
     auto load_patch = [&](int tile) {   // this group's patch <- tile; <= NP1 + NP0 DMAs per wave
         int n, y0, x0;
         coords(tile, n, y0, x0);
         if constexpr (TABLES) {
-            const unsigned base = ((unsigned)(n * a.H + y0 - 1) * (unsigned)a.W + (unsigned)(x0 - 1)) * (unsigned)C1;
+            const unsigned base = ((unsigned)(n * a.H + y0 - 1) * (unsigned)a.W + (unsigned)(x0 - 1)) * (unsigned)C1;   // element offset of the patch's first source pixel (may wrap: only used in-bounds)
 #pragma unroll
             for (int t = 0; t < NP1; ++t) {
                 if (wv * 64 + t * 256 >= NS1) break;   // wave-uniform
-                const int y = y0 - 1 + ((tb1[t] >> 20) & 15), x = x0 - 1 + ((tb1[t] >> 24) & 63);
+                const int y = y0 - 1 + halo_entry_row(tb1[t]), x = x0 - 1 + halo_entry_col(tb1[t]);
                 const bool ok = tb1[t] >= 0 && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-                glds16h(ok ? (const void *)(a.in1 + (base + (unsigned)(tb1[t] & 0xfffff))) : (const void *)g_zero_page_h,
-                        pb + NS0 * 16 + (wv * 64 + t * 256) * 16);
+                glds16(ok ? (const void *)(a.in1 + (base + halo_entry_off(tb1[t]))) : (const void *)g_halo_zero_page, pb + NS0 * 16 + (wv * 64 + t * 256) * 16);
             }
         } else {
             for (int base = wv * 64; base < NS1; base += 256) {
@@ -761,8 +680,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const int pr = pix / PW, pc = pix - pr * PW;
                 const int y = y0 - 1 + pr, x = x0 - 1 + pc;
                 const bool ok = pix < PH * PW && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-                const unsigned off = ((unsigned)(n * a.H + y) * (unsigned)a.W + (unsigned)x) * (unsigned)C1 + swz<SPP1>(phys, pc) * 8;
-                glds16h(ok ? (const void *)(a.in1 + off) : (const void *)g_zero_page_h, pb + NS0 * 16 + base * 16);
+                const unsigned off = ((unsigned)(n * a.H + y) * (unsigned)a.W + (unsigned)x) * (unsigned)C1 + halo_swz<SPP1>(phys, pc) * 8;
+                glds16(ok ? (const void *)(a.in1 + off) : (const void *)g_halo_zero_page, pb + NS0 * 16 + base * 16);
             }
         }
         if constexpr (C0 > 0) {
@@ -771,10 +690,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int t = 0; t < NP0; ++t) {
                 if (wv * 64 + t * 256 >= NS0) break;   // wave-uniform
-                const int y = (y0 >> 1) - 1 + ((tb0[t] >> 20) & 15), x = (x0 >> 1) - 1 + ((tb0[t] >> 24) & 63);
+                const int y = (y0 >> 1) - 1 + halo_entry_row(tb0[t]), x = (x0 >> 1) - 1 + halo_entry_col(tb0[t]);
                 const bool ok = tb0[t] >= 0 && (unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws;
-                glds16h(ok ? (const void *)(a.in0 + (base + (unsigned)(tb0[t] & 0xfffff))) : (const void *)g_zero_page_h,
-                        pb + (wv * 64 + t * 256) * 16);
+                glds16(ok ? (const void *)(a.in0 + (base + halo_entry_off(tb0[t]))) : (const void *)g_halo_zero_page, pb + (wv * 64 + t * 256) * 16);
             }
         }
     };
@@ -801,7 +719,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int ch = 0; ch < 2; ++ch) {
                     const int pr = wv + hr;
                     const int pc = ((ch * 16 + fj + kx - 1) >> 1) + 1;
-                    F.B[hr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(pb + ((pr * PW0 + pc) * (SPP0 ? SPP0 : 1) + swz<(SPP0 ? SPP0 : 4)>(kk * 4 + fq, pc)) * 16);
+                    F.B[hr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(pb + ((pr * PW0 + pc) * SPP0 + halo_swz<SPP0>(kk * 4 + fq, pc)) * 16);
                 }
         } else {
             const int kc = kk - KC0;
@@ -818,7 +736,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int ch = 0; ch < 2; ++ch) {
                     const int pr = 2 * wv + rr;
                     const int pc = ch * 16 + fj + kx;
-                    F.B[rr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(pb + NS0 * 16 + ((pr * PW + pc) * SPP1 + swz<SPP1>(kc * 4 + fq, pc)) * 16);
+                    F.B[rr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(pb + NS0 * 16 + ((pr * PW + pc) * SPP1 + halo_swz<SPP1>(kc * 4 + fq, pc)) * 16);
                 }
         }
     };
@@ -870,7 +788,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                     for (int ch = 0; ch < 2; ++ch) {
                         const int pr = 2 * wv + rr, pc = ch * 16 + fj + kx;
-                        B[rr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(pb + NS0 * 16 + ((pr * PW + pc) * SPP1 + swz<SPP1>(kc * 4 + fq, pc)) * 16);
+                        B[rr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(pb + NS0 * 16 + ((pr * PW + pc) * SPP1 + halo_swz<SPP1>(kc * 4 + fq, pc)) * 16);
                     }
                 load_A(g, 0, A[0]);
 #pragma unroll
@@ -1069,9 +987,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 template <int C0, int C1, int COUT, int COUT2 = 0>
 static int launch_halo_pp(const HaloArgs &a, hipStream_t s) {
-    constexpr int NS1 = round64(PH * PW * (C1 / 8));
-    constexpr int NS0 = C0 ? round64(PH0 * PW0 * (C0 / 8)) : 0;
-    constexpr int smem = 9 * (C0 + C1) / 8 * COUT * 16 + 2 * (NS0 + NS1) * 16 + 2 * COUT * 4 + 2 * COUT2 * 4;
+    constexpr int smem = 9 * (C0 + C1) / 8 * COUT * 16 + 2 * (ns0(C0) + ns1(C1)) * 16 + 2 * COUT * 4 + 2 * COUT2 * 4;
     static_assert(smem <= 160 * 1024, "LDS budget");
     int grid = 256;                       // one 8-wave workgroup per CU, persistent over tile pairs
     if (grid > a.n_tiles / 2) grid = a.n_tiles / 2;
@@ -1092,13 +1008,10 @@ static int launch_halo_pp(const HaloArgs &a, hipStream_t s) {
 // the other way -- every wave all four classes -- each would serve ONE).  The full-resolution (skip) half keeps its 9 taps, read with a column stride
 // of 2 pixels: its patch is stored as two COLUMN-PARITY planes (the DMA descriptors permute the pixels on their way in), so a fragment is again 16
 // consecutive pixels of one plane row and the swizzle of the dense form applies.  Per tile and wave: 136 MFMAs from 81 fragment reads (216 from 114).
-constexpr int PWH = PW / 2;   // columns per parity plane of the full-resolution patch
-
 template <int C0, int C1, int COUT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_halo_ppc_kernel(const HaloArgs a) {
     constexpr int SPP0 = C0 / 8, SPP1 = C1 / 8;
-    constexpr int NS1 = round64(2 * PH * PWH * SPP1);
-    constexpr int NS0 = round64(PH0 * PW0 * SPP0);
+    constexpr int NS1 = ns1_planes(C1), NS0 = ns0(C0);
     constexpr int PATCH_BYTES = (NS0 + NS1) * 16;
     constexpr int W_UP_BYTES = 16 * SPP0 * COUT * 16;      // [class][tap a*2+b][k-slot][COUT][8]
     constexpr int W_BYTES = W_UP_BYTES + 9 * SPP1 * COUT * 16;   // + [tap ky*3+kx][k-slot][COUT][8]
@@ -1126,50 +1039,29 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int fj = lane & 15, fq = lane >> 4;
     char *pb = s_patch + grp * PATCH_BYTES;
 
-    for (int off = wave * 1024; off < W_BYTES; off += 8192)
-        glds16h(reinterpret_cast<const char *>(a.w) + off + lane * 16, s_w + off);
+    for (int off = wave * 1024; off < W_BYTES; off += 8192) glds16(reinterpret_cast<const char *>(a.w) + off + lane * 16, s_w + off);
 
-    // per-lane DMA tables (see conv3x3_halo_body).  Full-resolution patch: LDS slot L -> (plane q, row pr, plane column cc, physical slot);
-    // the pixel it holds is patch column pc = 2 cc + q.
+    // per-lane DMA tables (see conv3x3_halo_body); the full-resolution patch as two column-parity planes (halo_geom.h: halo_entry_planes)
     constexpr int NP1 = (NS1 + 255) / 256, NP0 = (NS0 + 255) / 256;
     int tb1[NP1], tb0[NP0];
 #pragma unroll
-    for (int t = 0; t < NP1; ++t) {
-        const int L = wv * 64 + t * 256 + lane;
-        const int pix = L / SPP1, phys = L - pix * SPP1;
-        const int q = pix / (PH * PWH), rem = pix - q * (PH * PWH);
-        const int pr = rem / PWH, cc = rem - pr * PWH;
-        const int pc = 2 * cc + q;
-        tb1[t] = pix < 2 * PH * PWH ? (((pr * a.W + pc) * C1 + swz<SPP1>(phys, cc) * 8) | (pr << 20) | (pc << 24)) : -1;
-    }
+    for (int t = 0; t < NP1; ++t) tb1[t] = halo_entry_planes<SPP1>(a.W, C1, wv * 64 + t * 256 + lane);
 #pragma unroll
-    for (int t = 0; t < NP0; ++t) {
-        const int L = wv * 64 + t * 256 + lane;
-        const int pix = L / SPP0, phys = L - pix * SPP0;
-        const int pr = pix / PW0, pc = pix - pr * PW0;
-        tb0[t] = pix < PH0 * PW0 ? (((pr * (a.W >> 1) + pc) * C0 + swz<SPP0>(phys, pc) * 8) | (pr << 20) | (pc << 24)) : -1;
-    }
+    for (int t = 0; t < NP0; ++t) tb0[t] = halo_entry<PH0, PW0, SPP0, 1>(a.W, C0, wv * 64 + t * 256 + lane);
 
     const int txy = a.tiles_x * a.tiles_y;
-    auto coords = [&](int tile, int &n, int &y0, int &x0) {
-        n = tile / txy;
-        const int r = tile - n * txy;
-        const int ty = r / a.tiles_x;
-        y0 = ty * TH;
-        x0 = (r - ty * a.tiles_x) * TW;
-    };
+    auto coords = [&](int tile, int &n, int &y0, int &x0) { px_tile_coords<TH, TW>(a.tiles_x, txy, tile, n, y0, x0); };
     auto load_patch = [&](int tile) {   // this group's patch <- tile; NP1 + NP0 DMAs per wave at most
         int n, y0, x0;
         coords(tile, n, y0, x0);
         {
-            const unsigned base = ((unsigned)(n * a.H + y0 - 1) * (unsigned)a.W + (unsigned)(x0 - 1)) * (unsigned)C1;
+            const unsigned base = ((unsigned)(n * a.H + y0 - 1) * (unsigned)a.W + (unsigned)(x0 - 1)) * (unsigned)C1;   // element offset of the patch's first source pixel (may wrap: only used in-bounds)
 #pragma unroll
             for (int t = 0; t < NP1; ++t) {
                 if (wv * 64 + t * 256 >= NS1) break;   // wave-uniform
-                const int y = y0 - 1 + ((tb1[t] >> 20) & 15), x = x0 - 1 + ((tb1[t] >> 24) & 63);
+                const int y = y0 - 1 + halo_entry_row(tb1[t]), x = x0 - 1 + halo_entry_col(tb1[t]);
                 const bool ok = tb1[t] >= 0 && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-                glds16h(ok ? (const void *)(a.in1 + (base + (unsigned)(tb1[t] & 0xfffff))) : (const void *)g_zero_page_h,
-                        pb + NS0 * 16 + (wv * 64 + t * 256) * 16);
+                glds16(ok ? (const void *)(a.in1 + (base + halo_entry_off(tb1[t]))) : (const void *)g_halo_zero_page, pb + NS0 * 16 + (wv * 64 + t * 256) * 16);
             }
         }
         {
@@ -1178,10 +1070,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int t = 0; t < NP0; ++t) {
                 if (wv * 64 + t * 256 >= NS0) break;   // wave-uniform
-                const int y = (y0 >> 1) - 1 + ((tb0[t] >> 20) & 15), x = (x0 >> 1) - 1 + ((tb0[t] >> 24) & 63);
+                const int y = (y0 >> 1) - 1 + halo_entry_row(tb0[t]), x = (x0 >> 1) - 1 + halo_entry_col(tb0[t]);
                 const bool ok = tb0[t] >= 0 && (unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws;
-                glds16h(ok ? (const void *)(a.in0 + (base + (unsigned)(tb0[t] & 0xfffff))) : (const void *)g_zero_page_h,
-                        pb + (wv * 64 + t * 256) * 16);
+                glds16(ok ? (const void *)(a.in0 + (base + halo_entry_off(tb0[t]))) : (const void *)g_halo_zero_page, pb + (wv * 64 + t * 256) * 16);
             }
         }
     };
@@ -1205,7 +1096,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int pc = fj + b + px;
 #pragma unroll
             for (int r = 0; r < 5; ++r)
-                F.B[r] = *reinterpret_cast<const bf16x8_t *>(pb + (((py + r) * PW0 + pc) * SPP0 + swz<SPP0>(kc * 4 + fq, pc)) * 16);
+                F.B[r] = *reinterpret_cast<const bf16x8_t *>(pb + (((py + r) * PW0 + pc) * SPP0 + halo_swz<SPP0>(kc * 4 + fq, pc)) * 16);
         } else {
             const int h = g - 2 * KC0, kx = h / KC1, kc = h - kx * KC1;
 #pragma unroll
@@ -1216,7 +1107,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int q = (px + kx) & 1, cc = fj + ((px + kx) >> 1);
 #pragma unroll
             for (int r = 0; r < 9; ++r)
-                F.B[r] = *reinterpret_cast<const bf16x8_t *>(pb + NS0 * 16 + ((((q * PH) + py + r) * PWH + cc) * SPP1 + swz<SPP1>(kc * 4 + fq, cc)) * 16);
+                F.B[r] = *reinterpret_cast<const bf16x8_t *>(pb + NS0 * 16 + ((((q * PH) + py + r) * PWH + cc) * SPP1 + halo_swz<SPP1>(kc * 4 + fq, cc)) * 16);
         }
     };
     auto mma_group = [&](int g, const Frags &F) {
@@ -1316,9 +1207,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 template <int C0, int C1, int COUT>
 static int launch_halo_ppc(const HaloArgs &a, hipStream_t s) {
-    constexpr int NS1 = round64(2 * PH * PWH * (C1 / 8));
-    constexpr int NS0 = round64(PH0 * PW0 * (C0 / 8));
-    constexpr int smem = (16 * C0 + 9 * C1) / 8 * COUT * 16 + 2 * (NS0 + NS1) * 16 + 2 * COUT * 4;
+    constexpr int smem = (16 * C0 + 9 * C1) / 8 * COUT * 16 + 2 * (ns0(C0) + ns1_planes(C1)) * 16 + 2 * COUT * 4;
     static_assert(smem <= 160 * 1024, "LDS budget");
     int grid = 256;                       // one 8-wave workgroup per CU, persistent over tile pairs
     if (grid > (a.n_tiles + 1) / 2) grid = (a.n_tiles + 1) / 2;
@@ -1333,7 +1222,7 @@ static int launch_halo_sb(const HaloArgs &a, hipStream_t s) {
     // wave padding the LDS-DMA fill needs -- 39.25 KiB, which lets a 4th workgroup fit beside the slack rule below
     // (measured per launch at 320 maps: 2 / 3 / 4 workgroups per CU = 684 / 568 / 520 us).  The bf16-input layers get
     // SLOWER with a 4th workgroup (628 / 577 / 649 us) and keep the padded 40-KiB allocation = 3 per CU.
-    constexpr int smem = 9 * C1 / 8 * COUT * 16 + (BITS ? PH * PW * (C1 / 8) : round64(PH * PW * (C1 / 8))) * 16 +
+    constexpr int smem = 9 * C1 / 8 * COUT * 16 + (BITS ? PH * PW * (C1 / 8) : ns1(C1)) * 16 +
                          (COUT2 == 0 ? 2 * COUT * 4 : 0);   // + scale/shift
     int per_cu = (160 * 1024 - 2048) / smem;  // leave a little LDS slack: exactly-full allocations may not co-reside
     if (per_cu > 4) per_cu = 4;
@@ -1345,9 +1234,7 @@ static int launch_halo_sb(const HaloArgs &a, hipStream_t s) {
 
 template <int C0, int C1, int COUT, int COUT2, int EPI2>
 static int launch_halo(const HaloArgs &a, hipStream_t s) {
-    constexpr int NS1 = round64(PH * PW * (C1 / 8));
-    constexpr int NS0 = C0 ? round64(PH0 * PW0 * (C0 / 8)) : 0;
-    constexpr int smem = 9 * (C0 + C1) / 8 * COUT * 16 + 2 * (NS0 + NS1) * 16 + (COUT2 == 0 ? 2 * COUT * 4 : 0);
+    constexpr int smem = 9 * (C0 + C1) / 8 * COUT * 16 + 2 * (ns0(C0) + ns1(C1)) * 16 + (COUT2 == 0 ? 2 * COUT * 4 : 0);
     static_assert(smem <= 160 * 1024, "LDS budget");
     const int per_cu = (160 * 1024) / smem >= 2 ? 2 : 1;
     int grid = 256 * per_cu;

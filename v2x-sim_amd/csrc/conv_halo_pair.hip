@@ -26,10 +26,8 @@
 // stores -0.09, no layer-A MFMAs -0.07, no layer-B MFMAs -0.13, no barriers -0.08, no window fetch/expansion -0.06, no
 // layer-A epilogue -0.15 ms): the two waves a SIMD holds overlap little; the MFMA work alone would be 0.31 ms.
 #include "common.h"
+#include "halo_geom.h"   // tile, region and window extents; the patch layout of s_mid and its swizzle
 #include <cstdlib>
-
-typedef const __attribute__((address_space(1))) void *gptr_p_t;
-typedef __attribute__((address_space(3))) void *lptr_p_t;
 
 struct PairArgs {
     const uint32_t *bits;   // [N][H][W] occupancy words
@@ -46,9 +44,7 @@ struct PairArgs {
 };
 
 namespace pair {
-constexpr int TH = 8, TW = 32;          // output tile
-constexpr int MH = TH + 2, MW = TW + 2; // layer-A region (= layer B's input patch)
-constexpr int IH = TH + 4, IW = TW + 4; // input window
+using namespace halo;                   // TH x TW output tile, MH x MW layer-A region (= layer B's input patch), IH x IW input window
 constexpr int NMID = MH * MW;           // 340 pixels
 constexpr int NFRAG = (NMID + 15) / 16; // 22 linear fragments
 constexpr int FPW = (NFRAG + 3) / 4;    // fragments per wave (6; waves 2,3 use 5)
@@ -61,19 +57,6 @@ constexpr int LUT_BYTES = 256 * 16;     // byte of occupancy bits -> 8 bf16 {0,1
 #define V2X_PAIR_LDS_PAD_BUILD 0   // occupancy experiment (round 6, profiles/r06_pair_occupancy.txt): extra dynamic LDS per workgroup; 10240 -> 86 KiB = ONE workgroup per CU instead of two
 #endif
 constexpr int SMEM = 2 * W_BYTES + IN_BYTES + MID_BYTES + LUT_BYTES + V2X_PAIR_LDS_PAD_BUILD;
-#ifndef V2X_HALO_PSWZ_BUILD
-#define V2X_HALO_PSWZ_BUILD 1
-#endif
-// 1: (x >> 1) & 3 (round 1);  2: (x >> 2) & 3, whose fragment reads time 30 % faster in isolation and change nothing here (conv_halo.hip)
-__device__ __forceinline__ int swz4(int slot, int x) { return slot ^ ((x >> V2X_HALO_PSWZ_BUILD) & 3); }
-// ReLU on two packed bf16: as 16-bit integers a negative bf16 (sign bit) is a negative short, so max(x, 0) per half is
-// ONE v_pk_max_i16 for two values (fmaxf on the fp32 values costs two instructions EACH: it canonicalises first).
-// relu(round(v)) == round(relu(v)): rounding is monotone and -0 maps to +0 either way.
-typedef short v2x_s16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t x) {
-    const v2x_s16x2_t r = __builtin_elementwise_max(__builtin_bit_cast(v2x_s16x2_t, x), (v2x_s16x2_t){0, 0});
-    return __builtin_bit_cast(uint32_t, r);
-}
 __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -98,8 +81,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     // weights: linear LDS-DMA copies, resident for the whole kernel
     for (int off = wave * 1024; off < W_BYTES; off += 4096) {
-        __builtin_amdgcn_global_load_lds((gptr_p_t)(reinterpret_cast<const char *>(a.wA) + off + lane * 16), (lptr_p_t)(s_wA + off), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gptr_p_t)(reinterpret_cast<const char *>(a.wB) + off + lane * 16), (lptr_p_t)(s_wB + off), 16, 0, 0);
+        glds16(reinterpret_cast<const char *>(a.wA) + off + lane * 16, s_wA + off);
+        glds16(reinterpret_cast<const char *>(a.wB) + off + lane * 16, s_wB + off);
     }
 
     // tile-invariant per-lane geometry of the layer-A fragments of this wave
@@ -114,7 +97,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         in_off[t] = (fq & 1) * IN_PLANE + (r * IW + c) * 16;
         rc[t] = r | (c << 8) | ((p < NMID ? 1 : 0) << 16);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) mid_off[t][i] = ((r * MW + c) * 4 + swz4(i * 2 + (fq >> 1), c)) * 16 + (fq & 1) * 8;
+        for (int i = 0; i < 2; ++i) mid_off[t][i] = ((r * MW + c) * 4 + halo_swz<4>(i * 2 + (fq >> 1), c)) * 16 + (fq & 1) * 8;
     }
     // layer A walks K in 5 steps of TWO taps: k-groups 0,1 = the 16 channels of tap 2s, k-groups 2,3 = those of tap 2s+1
     // (channels 16..31 of the padded layer never enter an MFMA).  Per lane: window shift and weight slot of its tap.
@@ -137,9 +120,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // pending load costs an s_waitcnt vmcnt(0) at the top of every tile -- which, vmcnt being in-order, waits for the
     // previous tile's output stores.
     auto fetch_words = [&](int tile, uint32_t (&w)[2], uint32_t &okmask) {
-        const int n = tile / txy;
-        const int r = tile - n * txy;
-        const int ty = r / a.tiles_x, tx = r - ty * a.tiles_x;
+        int n, ty, tx;
+        halo_tile_index(a.tiles_x, txy, tile, n, ty, tx);
         uint32_t m = 0;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
@@ -207,9 +189,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int next = tile + walk.step;
         if (next < walk.end) fetch_words(next, words, okmask);   // lands under this tile's MFMAs
 
-        const int n = tile / txy;
-        const int rr_ = tile - n * txy;
-        const int ty = rr_ / a.tiles_x, tx = rr_ - ty * a.tiles_x;
+        int n, ty, tx;
+        halo_tile_index(a.tiles_x, txy, tile, n, ty, tx);
 
         // ---- (c) layer A on the 10 x 34 region, 22 linear fragments ---------------------------------------------
         {
@@ -252,8 +233,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     o.x = pack_bf16x2(v0, v1);
                     o.y = pack_bf16x2(v2, v3);
                     if (a.reluA) {
-                        o.x = relu_bf16x2(o.x);
-                        o.y = relu_bf16x2(o.y);
+                        o.x = v2x_relu_bf16x2(o.x);
+                        o.y = v2x_relu_bf16x2(o.y);
                     }
                     o.x = inside ? o.x : 0u;
                     o.y = inside ? o.y : 0u;
@@ -283,7 +264,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                     for (int ch = 0; ch < 2; ++ch) {
                         const int pr = 2 * wave + q, pc = ch * 16 + fj + kx;
-                        B[q * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(s_mid + ((pr * MW + pc) * 4 + swz4(fq, pc)) * 16);
+                        B[q * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(s_mid + ((pr * MW + pc) * 4 + halo_swz<4>(fq, pc)) * 16);
                     }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -322,8 +303,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     o.x = pack_bf16x2(v0, v1);
                     o.y = pack_bf16x2(v2, v3);
                     if (a.reluB) {
-                        o.x = relu_bf16x2(o.x);
-                        o.y = relu_bf16x2(o.y);
+                        o.x = v2x_relu_bf16x2(o.x);
+                        o.y = v2x_relu_bf16x2(o.y);
                     }
                     *reinterpret_cast<uint2 *>(a.out + ((size_t)(n * a.H + y) * a.W + x) * a.out_cstride + a.out_coff + co) = o;
                 }
@@ -357,7 +338,7 @@ extern "C" int v2x_conv2d_pair(const v2x_conv_desc *first, const v2x_conv_desc *
     V2X_REQUIRE(second->out && second->out_cstride >= 32 + second->out_coff && second->out_cstride % 4 == 0 && second->out_coff % 4 == 0,
                 "v2x_conv2d_pair: bad output view");
     V2X_REQUIRE(first->N == second->N && first->H == second->H && first->W == second->W, "v2x_conv2d_pair: extents differ");
-    V2X_REQUIRE(first->N >= 0 && first->H > 0 && first->W > 0 && first->H % pair::TH == 0 && first->W % pair::TW == 0,
+    V2X_REQUIRE(first->N >= 0 && first->H > 0 && first->W > 0 && first->H % halo::TH == 0 && first->W % halo::TW == 0,
                 "v2x_conv2d_pair: H %% 8 == 0 and W %% 32 == 0 required (H=%d W=%d)", first->H, first->W);
     V2X_REQUIRE((long long)first->N * first->H * first->W < (1ll << 31), "v2x_conv2d_pair: N*H*W must fit 31 bits");
     if (first->N == 0) return V2X_OK;
@@ -380,8 +361,8 @@ extern "C" int v2x_conv2d_pair(const v2x_conv_desc *first, const v2x_conv_desc *
     a.out = reinterpret_cast<uint16_t *>(second->out);
     a.out_cstride = second->out_cstride;
     a.out_coff = second->out_coff;
-    a.tiles_x = a.W / pair::TW;
-    a.tiles_y = a.H / pair::TH;
+    a.tiles_x = a.W / halo::TW;
+    a.tiles_y = a.H / halo::TH;
     a.n_tiles = a.N * a.tiles_x * a.tiles_y;
     int grid = v2x_num_cus() * 2;
     if (grid > a.n_tiles) grid = a.n_tiles;

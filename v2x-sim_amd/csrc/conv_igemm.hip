@@ -46,16 +46,8 @@ enum { EPI_BF16 = V2X_EPI_BF16, EPI_F32 = V2X_EPI_F32, EPI_GRU = V2X_EPI_GRU };
 // 64 B of zeros: padding taps / K-tail slots / out-of-range pixels point their LDS-DMA source here.
 static __device__ __attribute__((aligned(64))) unsigned int g_zero_page[16];
 
-typedef const __attribute__((address_space(1))) void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
-
-// 16 B per lane, global -> LDS without a VGPR round trip (global_load_lds_dwordx4).  The LDS
-// destination is wave-uniform base + lane*16, so the XOR swizzle lives in the per-lane SOURCE
-// address (guide rule 21): lane l fills physical slot (l&7) of row (l>>3) with logical slot
-// (l&7)^((l>>3)&7).
-__device__ __forceinline__ void glds16(const void *g, char *lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
+// The tiles come in by glds16 (common.h): its LDS destination is wave-uniform base + lane*16, so the XOR swizzle lives in the per-lane SOURCE
+// address (guide rule 21): lane l fills physical slot (l&7) of row (l>>3) with logical slot (l&7)^((l>>3)&7).
 
 template <int BCO, int BPX, int WCO, int WPX, int EPI>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {

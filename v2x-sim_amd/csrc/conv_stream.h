@@ -4,8 +4,6 @@
 #include "common.h"
 #include "stream_geom.h"
 
-typedef const __attribute__((address_space(1))) void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
 typedef const __attribute__((address_space(3))) float lds_cf_t;     // LDS-resident float (explicit address space: a generic pointer would be a FLAT load)
 typedef const __attribute__((address_space(3))) f32x4_t lds_cf4_t;   // (the builtin vector type: HIP's float4 class cannot be read through an address-space pointer)
 __device__ __forceinline__ float4 lds_ld4(lds_cf_t *p) {
@@ -13,12 +11,9 @@ __device__ __forceinline__ float4 lds_ld4(lds_cf_t *p) {
     return make_float4(v[0], v[1], v[2], v[3]);
 }
 
-__device__ __forceinline__ void glds16s(const void *g, char *lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
-// the same with a cache-policy field (aux: 2 = nt, 1 = sc0, 16 = sc1 on gfx950): round 6's experiment on the ConvGRU's two streams -- a non-temporal PATCH stream so that
+// glds16 (common.h) with a cache-policy field (aux: 2 = nt, 1 = sc0, 16 = sc1 on gfx950): round 6's experiment on the ConvGRU's two streams -- a non-temporal PATCH stream so that
 // the 5 MB of patches an XCD pulls per round stop evicting its 3.5 MB of weights from the 4-MiB L2 (the weights are re-fetched once per round: profiles/r06_fetch_calibration.txt).
-// Compile-time (-DV2X_STREAM8G_PATCH_AUX=n / -DV2X_STREAM8G_WEIGHT_AUX=n, tools/ab_build.sh); 0 = the default policy = glds16s.
+// Compile-time (-DV2X_STREAM8G_PATCH_AUX=n / -DV2X_STREAM8G_WEIGHT_AUX=n, tools/ab_build.sh); 0 = the default policy = glds16.
 #ifndef V2X_STREAM8G_PATCH_AUX
 #define V2X_STREAM8G_PATCH_AUX 0
 #endif
@@ -90,7 +85,7 @@ __device__ __forceinline__ void patch_col_table(int (&ct)[NC][3], int fj, int fq
 
 // descriptor -> address: the source of this lane's 16 bytes of 32-channel chunk kc of the concatenated NHWC operand (in0, C0 channels per pixel: the
 // first nc0 chunks; in1, C1: the others), or the zero page.  d = (source pixel index << 5) | (logical slot * 8 elements), -1 = zero page
-// (stream_geom.h: patch_desc).  The caller hands it to its LDS-DMA (glds16s / glds16s_aux) together with the piece's LDS address.
+// (stream_geom.h: patch_desc).  The caller hands it to its LDS-DMA (glds16 / glds16s_aux) together with the piece's LDS address.
 __device__ __forceinline__ const void *patch_src(const uint16_t *in0, unsigned C0, const uint16_t *in1, unsigned C1, int nc0, int kc, const void *zero_page, int d) {
     const bool first = kc < nc0;   // wave-uniform: the three selects are scalar
     const uint16_t *src = first ? in0 : in1;

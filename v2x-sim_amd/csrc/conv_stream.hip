@@ -395,8 +395,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     auto issue_weights = [&](int s) {  // slice of step s -> ring slot s % RING ; NW instructions
         char *dst = s_ring + (s & (RING - 1)) * SLICE_BYTES;
         const uint16_t *src = wsrc + (size_t)s * (BCO * 32);
-        glds16s(src, dst + wave * 1024);
-        if (NW == 2) glds16s(src + 4 * 512, dst + (wave + 4) * 1024);
+        glds16(src, dst + wave * 1024);
+        if (NW == 2) glds16(src + 4 * 512, dst + (wave + 4) * 1024);
     };
     auto issue_patch_piece = [&](int kc, int t, int buf) {  // piece wave+4t of chunk kc's patch
         const bool first = kc < nc0;
@@ -405,9 +405,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         int d = hf ? pd_half[0] : pd_full[0];
 #pragma unroll
         for (int u = 1; u < 6; ++u) d = (t == u) ? (hf ? pd_half[u] : pd_full[u]) : d;
-        glds16s(patch_src(a.in0, a.C0, a.in1, a.C1, nc0, kc, zero_page, d), s_patch + buf * PATCH_BYTES + (wave + 4 * t) * 1024);
+        glds16(patch_src(a.in0, a.C0, a.in1, a.C1, nc0, kc, zero_page, d), s_patch + buf * PATCH_BYTES + (wave + 4 * t) * 1024);
     };
-    auto issue_dummy = [&]() { glds16s(zero_page, s_dummy); };
+    auto issue_dummy = [&]() { glds16(zero_page, s_dummy); };
 
     // ---- prologue: whole patch of chunk 0 (6 pieces per wave), weight slices of steps 0..2 --------
 #pragma unroll
@@ -623,13 +623,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     const bool has_w = wave < W_PIECES;                       // wave-uniform
     const uint16_t *wsrc = wbase + lane * 8 + wave * 512;
-    auto issue_dummy = [&]() { glds16s(zero_page, s_dummy); };
+    auto issue_dummy = [&]() { glds16(zero_page, s_dummy); };
     auto issue_slice = [&](int slice, int slot, bool real) {  // exactly one DMA
-        if (has_w && real) glds16s(wsrc + (size_t)slice * (BCO * 32), s_ring + slot * SLICE_BYTES + wave * 1024);
+        if (has_w && real) glds16(wsrc + (size_t)slice * (BCO * 32), s_ring + slot * SLICE_BYTES + wave * 1024);
         else issue_dummy();
     };
     auto issue_piece = [&](int d, int kc, int t, int buf) {   // exactly one DMA; d = descriptor of this lane
-        glds16s(patch_src(a.in0, a.C0, a.in1, a.C1, nc0, kc, zero_page, d), s_patch + buf * PATCH8_BYTES + (wave + 8 * t) * 1024);
+        glds16(patch_src(a.in0, a.C0, a.in1, a.C1, nc0, kc, zero_page, d), s_patch + buf * PATCH8_BYTES + (wave + 8 * t) * 1024);
     };
     const bool chunk0_half = (nc0 > 0) && a.up0;
 
@@ -1265,7 +1265,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     const uint16_t *wsrc = wbase + lane * 8 + wave * 512;
     auto issue_weights = [&](int s) {   // one DMA (BCO = 64: 4 pieces, one per wave)
-        glds16s(wsrc + (size_t)s * (BCO * 32), s_ring + (s & (RING - 1)) * SLICE_BYTES + wave * 1024);
+        glds16(wsrc + (size_t)s * (BCO * 32), s_ring + (s & (RING - 1)) * SLICE_BYTES + wave * 1024);
     };
     auto issue_patch = [&](int kc, bool hf) {
         const bool first = kc < nc0;
@@ -1278,7 +1278,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             int d = pd[t];
             asm volatile("" : "+v"(d));   // keep the address arithmetic HERE: hoisted out of the chunk loop it becomes ten
                                           // live 64-bit addresses on top of 176 busy registers (it spilled)
-            glds16s(patch_src(src, cs, first ? kc : kc - nc0, zero_page, d), s_patch + (wave + 4 * t) * 1024);
+            glds16(patch_src(src, cs, first ? kc : kc - nc0, zero_page, d), s_patch + (wave + 4 * t) * 1024);
         }
     };
 
@@ -1396,7 +1396,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int slot = st % 3;
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
-            glds16s(wsrc + (size_t)(kc * 9 + ky * 3 + kx) * (BCO * 32), s_ring + slot * STEP_BYTES + ky * SLICE_BYTES + wave * 1024);
+            glds16(wsrc + (size_t)(kc * 9 + ky * 3 + kx) * (BCO * 32), s_ring + slot * STEP_BYTES + ky * SLICE_BYTES + wave * 1024);
     };
     auto issue_patch = [&](int kc, bool hf) {
         const bool first = kc < nc0;
@@ -1408,7 +1408,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if (wave + 4 * t >= npieces) break;              // wave-uniform
             int d = pd[t];
             asm volatile("" : "+v"(d));
-            glds16s(patch_src(src, cs, first ? kc : kc - nc0, zero_page, d), s_patch + (wave + 4 * t) * 1024);
+            glds16(patch_src(src, cs, first ? kc : kc - nc0, zero_page, d), s_patch + (wave + 4 * t) * 1024);
         }
     };
 

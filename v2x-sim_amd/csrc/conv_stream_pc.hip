@@ -83,7 +83,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- LDS-DMA issue helpers (one instruction = one 1-KiB piece) ------------------------------------------------------------------------
     auto issue_up_patch_piece = [&](int n, int y0, int x0, int kc, int piece, int buf_off) {   // half-resolution patch of up chunk kc
         const int d = patch_desc<pcs::TH, pcs::TW, pcs::PSH>(a.H, a.W, n, y0, x0, piece * 64 + fresh_lane(), true);
-        glds16s(patch_src(a.in0, (unsigned)a.C0, kc, zero_page, d), smem + buf_off + piece * 1024);
+        glds16(patch_src(a.in0, (unsigned)a.C0, kc, zero_page, d), smem + buf_off + piece * 1024);
     };
     auto issue_sk_patch_piece = [&](int n, int y0, int x0, int kc, int piece, int buf_off) {   // full-resolution patch of skip chunk kc, two parity planes
         const int L = piece * 64 + fresh_lane();
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int y = y0 - 1 + pr, x = x0 - 1 + 2 * cc + q;
         const bool ok = pix < 2 * PHF * PWH && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
         const unsigned off = (unsigned)((n * a.H + y) * a.W + x) * (unsigned)a.C1 + (unsigned)(kc * 32 + ((phys ^ patch_swz<pcs::PSH>(cc)) << 3));
-        glds16s(ok ? (const void *)(a.in1 + off) : zero_page, smem + buf_off + piece * 1024);
+        glds16(ok ? (const void *)(a.in1 + off) : zero_page, smem + buf_off + piece * 1024);
     };
     auto issue_up_weights = [&](int st, int first, int count) {   // pieces [first, first + count) of up step st's 32-KiB slot image
         const int lane_w = fresh_lane();
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         char *dst = smem + (st % NU) * USTEP;
 #pragma unroll
         for (int u = 0; u < 12; ++u)
-            if (u < count) glds16s(src + (first + u) * 1024, dst + (first + u) * 1024);
+            if (u < count) glds16(src + (first + u) * 1024, dst + (first + u) * 1024);
     };
     auto issue_sk_weights = [&](int st, int first, int count) {   // pieces of skip step st's 24-KiB slot image
         const int lane_w = fresh_lane();
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         char *dst = smem + (st % 3) * SSTEP;
 #pragma unroll
         for (int u = 0; u < 6; ++u)
-            if (u < count) glds16s(src + (first + u) * 1024, dst + (first + u) * 1024);
+            if (u < count) glds16(src + (first + u) * 1024, dst + (first + u) * 1024);
     };
     auto up_buf = [&](int kc) { return ((n_up - 1 - kc) & 1) ? OFF_UPB : OFF_UPA; };   // the last up chunk sits in UPA
     auto sk_buf = [&](int kc) { return (kc & 1) ? OFF_P0 : OFF_P1; };                  // the first skip chunk in P1
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
     auto issue_up_patch_piece = [&](int n, int y0, int x0, int kc, int piece, int buf_off) {
         const int d = patch_desc<pcs::TH, pcs::TW, pcs::PSH>(a.H, a.W, n, y0, x0, piece * 64 + fresh_lane(), true);
-        glds16s(patch_src(a.in0, (unsigned)a.C0, kc, zero_page, d), smem + buf_off + piece * 1024);
+        glds16(patch_src(a.in0, (unsigned)a.C0, kc, zero_page, d), smem + buf_off + piece * 1024);
     };
     auto issue_sk_patch_piece = [&](int n, int y0, int x0, int kc, int piece, int buf_off) {
         const int L = piece * 64 + fresh_lane();
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int y = y0 - 1 + pr, x = x0 - 1 + 2 * cc + q;
         const bool ok = pix < 2 * PHF * PWH && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
         const unsigned off = (unsigned)((n * a.H + y) * a.W + x) * (unsigned)a.C1 + (unsigned)(kc * 32 + ((phys ^ patch_swz<pcs::PSH>(cc)) << 3));
-        glds16s(ok ? (const void *)(a.in1 + off) : zero_page, smem + buf_off + piece * 1024);
+        glds16(ok ? (const void *)(a.in1 + off) : zero_page, smem + buf_off + piece * 1024);
     };
     auto issue_up_weights = [&](int st, int first, int count) {
         const int lane_w = fresh_lane();
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         char *dst = smem + (st % 3) * USTEP;
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-            if (u < count) glds16s(src + (first + u) * 1024, dst + (first + u) * 1024);
+            if (u < count) glds16(src + (first + u) * 1024, dst + (first + u) * 1024);
     };
     auto issue_sk_weights = [&](int st, int first, int count) {
         const int lane_w = fresh_lane();
@@ -410,7 +410,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         char *dst = smem + (st % 3) * SSTEP;
 #pragma unroll
         for (int u = 0; u < 3; ++u)
-            if (u < count) glds16s(src + (first + u) * 1024, dst + (first + u) * 1024);
+            if (u < count) glds16(src + (first + u) * 1024, dst + (first + u) * 1024);
     };
     auto up_buf = [&](int kc) { return OFF_UP + (grp * 2 + (kc & 1)) * (UP_PIECES * 1024); };
     const int sk_buf = OFF_SP + grp * (SP_PIECES * 1024);

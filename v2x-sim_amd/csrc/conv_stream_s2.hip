@@ -147,14 +147,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) voi
     auto issue_weights = [&](int s) {   // NW DMAs
         char *dst = s_ring + (s & (S2_RING - 1)) * SLICE_BYTES;
         const uint16_t *src = wsrc + (size_t)s * (BCO * 32);
-        glds16s(src, dst + wave * 1024);
-        if (NW == 2) glds16s(src + 4 * 512, dst + (wave + 4) * 1024);
+        glds16(src, dst + wave * 1024);
+        if (NW == 2) glds16(src + 4 * 512, dst + (wave + 4) * 1024);
     };
     auto issue_patch = [&](int kc) {    // this wave's pieces of chunk kc (pieces >= S2_PIECES do not exist)
 #pragma unroll
         for (int t = 0; t < G::PPW; ++t) {
             if (wave + 4 * t >= G::PIECES) break;            // wave-uniform
-            glds16s(patch_src(a.in, (unsigned)a.C, kc, zero_page, pd[t]), s_patch + (wave + 4 * t) * 1024);
+            glds16(patch_src(a.in, (unsigned)a.C, kc, zero_page, pd[t]), s_patch + (wave + 4 * t) * 1024);
         }
     };
 
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     // weights of the (single) channel tile: one linear LDS-DMA copy
     for (int off = wave * 1024; off < W_BYTES; off += 4096)
-        glds16s(reinterpret_cast<const char *>(a.w) + off + lane * 16, s_w + off);
+        glds16(reinterpret_cast<const char *>(a.w) + off + lane * 16, s_w + off);
 
     int ct[2][3];
 #pragma unroll
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int y = 2 * y0 - 1 + (d >> 20), x = 2 * x0 - 1 + ((d >> 8) & 0xfff);
             const bool ok = d >= 0 && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
             const unsigned off = ((unsigned)(n * a.H + y) * (unsigned)a.W + (unsigned)x) * (unsigned)a.C + (unsigned)(d & 0xff);
-            glds16s(ok ? (const void *)(a.in + off) : zero_page, s_patch + (wave + 4 * t) * 1024);
+            glds16(ok ? (const void *)(a.in + off) : zero_page, s_patch + (wave + 4 * t) * 1024);
         }
         wait_vmcnt<0>();     // the patch (and, the first time, the weights; later also the previous tile's stores)
         __builtin_amdgcn_s_barrier();
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
     auto issue_piece = [&](int d, int kc, char *dst) {
         if constexpr ((DBG & 2) != 0) return;
-        glds16s(patch_src(a.in, (unsigned)a.C, kc, zero_page, d), dst);
+        glds16(patch_src(a.in, (unsigned)a.C, kc, zero_page, d), dst);
     };
     // piece p = wv + 4u of step t (chunk t / 3, tap column j = t % 3 -> kx = 0, 2, 1); piece p = (tap row p / 8, piece p % 8 of its slice):
     // a wave's first two pieces (u = 0, 1) are tap row 0
@@ -515,7 +515,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int kx = j == 0 ? 0 : (j == 1 ? 2 : 1);
         const int p = wv + 4 * u;
         const int ky = p >> 3, pis = p & 7;
-        glds16s(wbase + (size_t)(kc * 9 + ky * 3 + kx) * (BCO * 32) + pis * 512 + lw * 8, s_ring + slot * STEP_BYTES + ky * SLICE_BYTES + pis * 1024);
+        glds16(wbase + (size_t)(kc * 9 + ky * 3 + kx) * (BCO * 32) + pis * 512 + lw * 8, s_ring + slot * STEP_BYTES + ky * SLICE_BYTES + pis * 1024);
     };
     // s_waitcnt vmcnt(K) for the wave-uniform run-time K in {0, 4, 6, 8, 9} (+ N_ST)
     auto wait_keep = [&](int k, bool plus_stores) {

@@ -30,16 +30,12 @@
 // K order and epilogue arithmetic are those of the stand-alone kernels: the logits are bit-identical to v2x_conv2d(conv8_2) followed by
 // v2x_conv2d(heads) (tests/test_gpu_tail.py).  The recompute of conv8_2 on the halo ring costs 22/16 of its MFMAs.
 #include "conv_stream.h"   // lds_ld4: LDS table reads through an explicit address-space pointer
+#include "halo_geom.h"     // tile, region and window extents; the patch layout of the window and of s_mid, its swizzle; the zero page
 #include <cstdlib>
-
-typedef const __attribute__((address_space(1))) void *gptr_tl_t;
-typedef __attribute__((address_space(3))) void *lptr_tl_t;
 
 typedef unsigned int u32x2_tl_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) u32x2_tl_t lds_u2_t;   // stage A's results go to LDS through an EXPLICIT address-space pointer: behind a generic
                                                                   // one the compiler orders the write after every LDS-DMA in flight (s_waitcnt vmcnt(0))
-
-static __device__ __attribute__((aligned(64))) unsigned int g_zero_page_tail[16];
 
 struct TailArgs {
     const uint16_t *in;                 // conv8_1's output [N][H][W][in_cstride] bf16 (32 channels at in_coff)
@@ -62,9 +58,7 @@ struct TailArgs {
 
 // (the build-time experiment switches of this kernel -- scheduling fences, group offset, phase removal, time stamps -- live in tools/probes/conv_tail_probe.hip)
 namespace tail {
-constexpr int TH = 8, TW = 32;
-constexpr int MH = TH + 2, MW = TW + 2;     // stage-A region = stage B's patch
-constexpr int IH = TH + 4, IW = TW + 4;     // input window
+using namespace halo;                       // TH x TW output tile, MH x MW stage-A region (= stage B's patch), IH x IW input window
 constexpr int NMID = MH * MW;               // 340
 constexpr int WA_BYTES = 36 * 32 * 16;      // 18 432
 constexpr int WB_BYTES = 36 * 64 * 16;      // 36 864
@@ -78,7 +72,6 @@ constexpr int OFF_DUMMY = OFF_GRP + 2 * GRP_BYTES;
 constexpr int OFF_TAB = OFF_DUMMY + 1024;
 constexpr int SMEM = OFF_TAB + 288 * 4;     // (12 fp32 dwordx4 stores per wave and tile: 3 channel tiles x 4 fragments -- the counted wait below)
 static_assert(IN_BYTES % 1024 == 0 && SMEM <= 160 * 1024, "LDS map");
-__device__ __forceinline__ int swz4(int slot, int x) { return slot ^ ((x >> 1) & 3); }
 }  // namespace tail
 
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_tail_kernel(const TailArgs a) {
@@ -95,7 +88,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // the three weight sets: wA and wB by LDS-DMA (resident), the 1x1's fragments in registers
     for (int off = wave8 * 1024; off < WA_BYTES + WB_BYTES; off += 8192) {
         const char *src = off < WA_BYTES ? reinterpret_cast<const char *>(a.wA) + off : reinterpret_cast<const char *>(a.wB) + (off - WA_BYTES);
-        __builtin_amdgcn_global_load_lds((gptr_tl_t)(src + lane * 16), (lptr_tl_t)(smem + off), 16, 0, 0);
+        glds16(src + lane * 16, smem + off);
     }
     bf16x8_t w2f[3][2];
 #pragma unroll
@@ -133,7 +126,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
             const int col = 1 + 16 * sg + fj + kx;
-            body_off[sg][kx] = (col * 4 + swz4(fq, col)) * 16;
+            body_off[sg][kx] = halo_frag_off<IW, 4>(0, col, fq);   // inside a window row: row 0
         }
     // halo fragment: wave 2 -- lanes 0 .. 9 = column 0 rows 0 .. 9, lanes 10 .. 15 = column 33 rows 0 .. 5;  wave 3 -- lanes 0 .. 3 = column 33 rows 6 .. 9
     int hr, hc, hvalid;
@@ -145,22 +138,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         hvalid = (wave >= 2 && q < 20) ? 1 : 0;
     }
     const int txy = a.tiles_x * a.tiles_y;
-    auto tile_coords = [&](int tile, int &n, int &ty, int &tx) {
-        n = tile / txy;
-        const int r = tile - n * txy;
-        ty = r / a.tiles_x;
-        tx = r - ty * a.tiles_x;
-    };
+    auto tile_coords = [&](int tile, int &n, int &ty, int &tx) { halo_tile_index(a.tiles_x, txy, tile, n, ty, tx); };
     // (fresh_lane(), conv_stream.h: recomputed where it is used -- lane-derived DMA addresses hoisted out of the tile loop cost ~30 registers (spills))
     // window fill: the lane's element offset from the window's first pixel per piece (tile-invariant: 7 registers); a tile away from the image border
     // (70 % of them at 256 x 256) needs no bounds test -- 3 VALU instructions per piece instead of ~15
     unsigned woff[PPW];
 #pragma unroll
     for (int u = 0; u < PPW; ++u) {
-        const int sidx = (wave + 4 * u) * 64 + lane;
-        const int pix = sidx >> 2, phys = sidx & 3;
-        const int pr = pix / IW, pcx = pix - pr * IW;
-        woff[u] = (unsigned)(pr * a.W + pcx) * (unsigned)a.in_cstride + (unsigned)(swz4(phys, pcx) * 8);
+        woff[u] = halo_window_rel(a.W, a.in_cstride, (wave + 4 * u) * 64 + lane);
     }
     auto load_window = [&](int tile) {   // exactly PPW DMAs per wave (the fourth wave's 7th goes to a dummy page)
         int n, ty, tx;
@@ -172,7 +157,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int u = 0; u < PPW; ++u) {
                 const int piece = wave + 4 * u;
                 char *dst = piece < IN_PIECES ? s_in + piece * 1024 : smem + OFF_DUMMY;   // wave-uniform
-                __builtin_amdgcn_global_load_lds((gptr_tl_t)(piece < IN_PIECES ? (const void *)(base + woff[u]) : (const void *)g_zero_page_tail), (lptr_tl_t)dst, 16, 0, 0);
+                glds16(piece < IN_PIECES ? (const void *)(base + woff[u]) : (const void *)g_halo_zero_page, dst);
             }
             return;
         }
@@ -185,9 +170,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int pr = pix / IW, pcx = pix - pr * IW;
             const int y = ty * TH - 2 + pr, x = tx * TW - 2 + pcx;
             const bool ok = piece < IN_PIECES && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-            const unsigned off = (unsigned)((n * a.H + y) * a.W + x) * (unsigned)a.in_cstride + (unsigned)(a.in_coff + swz4(phys, pcx) * 8);
+            const unsigned off = (unsigned)((n * a.H + y) * a.W + x) * (unsigned)a.in_cstride + (unsigned)(a.in_coff + halo_swz<4>(phys, pcx) * 8);
             char *dst = piece < IN_PIECES ? s_in + piece * 1024 : smem + OFF_DUMMY;   // wave-uniform
-            __builtin_amdgcn_global_load_lds((gptr_tl_t)(ok ? (const void *)(a.in + off) : (const void *)g_zero_page_tail), (lptr_tl_t)dst, 16, 0, 0);
+            glds16(ok ? (const void *)(a.in + off) : (const void *)g_halo_zero_page, dst);
         }
     };
 
@@ -240,7 +225,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 } else {
                     const int col = hc + kx;
 #pragma unroll
-                    for (int ky = 0; ky < 3; ++ky) X[ky] = *reinterpret_cast<const bf16x8_t *>(s_in + (((hr + ky) * IW + col) * 4 + swz4(fq, col)) * 16);
+                    for (int ky = 0; ky < 3; ++ky) X[ky] = *reinterpret_cast<const bf16x8_t *>(s_in + halo_frag_off<IW, 4>(hr + ky, col, fq));
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -279,7 +264,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     o.y = v2x_relu_bf16x2_floor(pack_bf16x2(v[i][2] * scA[i].z + shA[i].z, v[i][3] * scA[i].w + shA[i].w), floorA);
                     o.x = inside ? o.x : 0u;
                     o.y = inside ? o.y : 0u;
-                    if (keep) *(lds_u2_t *)(s_mid + ((r * MW + c) * 4 + swz4(i * 2 + (fq >> 1), c)) * 16 + (fq & 1) * 8) = (u32x2_tl_t){o.x, o.y};
+                    if (keep) *(lds_u2_t *)(s_mid + halo_frag_off<MW, 4>(r, c, i * 2 + (fq >> 1)) + (fq & 1) * 8) = (u32x2_tl_t){o.x, o.y};
                 }
             };
             // body fragments: their columns are the tile's own (always inside the image); a row is outside only for the first / last tile row (wave-uniform)
@@ -319,8 +304,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int rr = 0; rr < 4; ++rr)
 #pragma unroll
                     for (int ch = 0; ch < 2; ++ch) {
-                        const int pr = 2 * wave + rr, pc = ch * 16 + fj + kx;
-                        B[rr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(s_mid + ((pr * MW + pc) * 4 + swz4(fq, pc)) * 16);
+                        B[rr * 2 + ch] = *reinterpret_cast<const bf16x8_t *>(s_mid + halo_frag_off_full<4>(2 * wave + rr, ch * 16 + fj, kx, fq));
                     }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) A[0][i] = *reinterpret_cast<const bf16x8_t *>(s_wB + ((kx * 4 + fq) * 64 + i * 16 + fj) * 16);
@@ -424,7 +408,7 @@ int v2x_conv_tail_dispatch(const v2x_conv_desc *first, const v2x_conv_desc *seco
                     second->scale2 && second->shift2 && second->out && second->out2,
                 "v2x_conv2d_pair (tail form): null pointer");
     V2X_REQUIRE(first->N == second->N && first->H == second->H && first->W == second->W, "v2x_conv2d_pair (tail form): extents differ");
-    V2X_REQUIRE(first->N >= 0 && first->H > 0 && first->W > 0 && first->H % tail::TH == 0 && first->W % tail::TW == 0,
+    V2X_REQUIRE(first->N >= 0 && first->H > 0 && first->W > 0 && first->H % halo::TH == 0 && first->W % halo::TW == 0,
                 "v2x_conv2d_pair (tail form): H %% 8 == 0 and W %% 32 == 0 required (H=%d W=%d)", first->H, first->W);
     V2X_REQUIRE((long long)first->N * first->H * first->W < (1ll << 27), "v2x_conv2d_pair (tail form): N*H*W must stay below 2^27 (32-bit element offsets)");
     V2X_REQUIRE(second->out_cstride >= second->split + second->out_coff && second->out_cstride % 4 == 0 && second->out_coff % 4 == 0 &&
@@ -456,8 +440,8 @@ int v2x_conv_tail_dispatch(const v2x_conv_desc *first, const v2x_conv_desc *seco
     a.out_cstride = second->out_cstride;
     a.out_coff = second->out_coff;
     a.out2_cstride = second->out2_cstride;
-    a.tiles_x = a.W / tail::TW;
-    a.tiles_y = a.H / tail::TH;
+    a.tiles_x = a.W / halo::TW;
+    a.tiles_y = a.H / halo::TH;
     a.n_tiles = a.N * a.tiles_x * a.tiles_y;
     a.xcd_walk = v2x_tune(V2X_TUNE_HALO_XCD);
     return tail_launch(a, stream);
